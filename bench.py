@@ -30,10 +30,17 @@ sample of every rank's reads is checked against the oracle on rank 0.  A
 rank count that does not match --gpus, or more RCCL ranks than visible GPUs,
 is an error, never a silent 1-GPU run.
 
-Output: ONE JSON line on rank 0 with the driver contract fields plus
-"roofline" (dominant kernel, HIP events on the library stream) and
-"cpu_baseline" (the C++ oracle restatement of the reference align on a
-bounded sample of the same reads, rank 0 at N=1 only, median of 3).
+Output: ONE JSON line on rank 0 with the driver contract fields.  A plain run
+does only what the headline needs: set-up, warm-up, the timed steps, the line
+(with the timed region's own per-kernel event times in `extra`).  `--full`
+adds what takes runs of its own after the timed steps: "roofline" (dominant
+kernel, HIP events on the library stream, on a quiet GPU), the reads-resident
+rate, the host check of mid_occ, the oracle parity sample and "cpu_baseline"
+(the C++ oracle restatement of the reference align on a bounded sample of the
+same reads, rank 0 at N=1 only, median of 3); those fields are null without it.
+`--dump-outputs DIR` writes what the last timed step returned (per-read
+results and PAF text) as .npy files; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -108,6 +115,11 @@ def parse(argv=None):
     p.add_argument("--min-chain-score", type=int, default=40, help="-m (main.rs:48)")
     p.add_argument("--iso-batches", type=int, default=3,
                    help="batches mapped by one context after the timed region for the roofline's quiet-GPU launch times")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything that is not the headline figure: host mid_occ check, "
+                        "reads resident in HBM, quiet-GPU roofline, oracle parity sample, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (per-read results, PAF text) as DIR/<name>.npy")
     args = p.parse_args(argv)
     if args.shares < 0:
         args.shares = 1 if args.reads <= 2000 else 2
@@ -224,6 +236,43 @@ def paf_lines_by_read(paf: bytes):
         nm = ln.split(b"\t", 1)[0].decode()
         out[nm] = out[nm] + b"\n" + ln if nm in out else ln
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs writes at most this much over all its files
+
+
+def dump_arrays(res: np.ndarray, paf: bytes, budget: int = DUMP_MAX_BYTES):
+    """What one step hands its caller, as plain arrays: the per-read results
+    (RES_DTYPE, one float64 column per field in field order: every field is exact
+    in float64) and the PAF text (one float32 per byte).  Over `budget` bytes a
+    fixed seeded sample is kept instead: reads (rows) for the results, whole lines
+    for the text, each in its original order.  -> {file stem: array}"""
+    rows = np.stack([res[f].astype(np.float64) for f in RES_DTYPE.names], axis=1) if len(res) else np.zeros((0, len(RES_DTYPE.names)))
+    rng = np.random.default_rng(64)
+    half = budget // 2
+    if rows.nbytes > half:
+        keep = np.sort(rng.choice(len(rows), size=half // (8 * rows.shape[1]), replace=False))
+        rows = rows[keep]
+    if 4 * len(paf) > half:
+        lines = paf.splitlines(keepends=True)
+        out, room = [], half // 4
+        for i in rng.permutation(len(lines)):
+            if len(lines[i]) <= room:
+                out.append(i)
+                room -= len(lines[i])
+        paf = b"".join(lines[i] for i in sorted(out))
+    return {"results": np.ascontiguousarray(rows), "paf_bytes": np.frombuffer(paf, dtype=np.uint8).astype(np.float32)}
+
+
+def dump_outputs(path: str, rank: int, last_units) -> None:
+    """--dump-outputs: the last timed step's units (in read order) -> DIR/results.npy
+    and DIR/paf_bytes.npy (ranks > 0: <name>_rank<r>.npy)."""
+    us = sorted(last_units, key=lambda u: u["k"])
+    res = np.concatenate([np.frombuffer(u["res"], dtype=RES_DTYPE, count=u["n"]) for u in us if u["n"]] or [np.zeros(0, RES_DTYPE)])
+    paf = b"".join(bytes(u["buf"].raw[:u["len"]]) for u in us)
+    os.makedirs(path, exist_ok=True)
+    for name, a in dump_arrays(res, paf).items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
 
 
 def kernel_sha() -> str:
@@ -508,9 +557,11 @@ def main():
             os.unlink(shm)
     index_from, index_note = idx.origin               # what actually happened (mm2g_index_origin)
     t_index = time.time() - t0
-    t0 = time.time()
-    mid_host = idx.calc_mid_occ(2e-4)            # the reference's sort of all counts (index.rs:124-141)
-    t_mid_host = time.time() - t0
+    mid_host = t_mid_host = None
+    if args.full:
+        t0 = time.time()
+        mid_host = idx.calc_mid_occ(2e-4)        # the reference's sort of all counts (index.rs:124-141)
+        t_mid_host = time.time() - t0
     log(f"rank {rank}: index from {index_from}{' (' + index_note + ')' if index_note else ''} in {t_index:.1f}s, stats {idx.stats()}")
 
     S = max(1, args.streams)
@@ -528,7 +579,7 @@ def main():
     t0 = time.time()
     mid_dev = devs[0].index_mid_occ(2e-4)
     t_mid_dev = time.time() - t0
-    if mid_dev != mid_host:
+    if args.full and mid_dev != mid_host:
         raise SystemExit(f"bench.py: device mid_occ {mid_dev} != host {mid_host}")
     mid = max(mid_dev, 10)                       # main.rs:196-197
     devs[0].set_mid_occ(mid)
@@ -536,7 +587,7 @@ def main():
         d.share_index(devs[0], mid)
     idx.release_tables()                         # the device copy is made: keep only names/lengths on the host
     log(f"rank {rank}: index upload {t_up:.1f}s ({S} contexts share it), mid_occ {mid} "
-        f"(device {t_mid_dev * 1e3:.1f} ms, host sort {t_mid_host * 1e3:.0f} ms)")
+        f"(device {t_mid_dev * 1e3:.1f} ms" + (f", host sort {t_mid_host * 1e3:.0f} ms)" if args.full else ")"))
 
     opts = M.map_opts(min_cnt=args.min_cnt, min_chain_score=args.min_chain_score)
     multi = args.min_cnt <= 1 and args.min_chain_score <= 15   # the -n <= 1 -m <= k multi-chain output (k = 15)
@@ -631,10 +682,12 @@ def main():
     hm = np.array([u["host_ms"] for u in timed])
     host_ms = dict(zip(("set_reads", "map_enqueue", "results_wait", "format_paf"), [round(float(x), 3) for x in hm.mean(axis=0)]))
     my_bases = sum(bases_per_batch[s % n_batches] for s in range(w_eff, w_eff + args.steps))
+    if args.dump_outputs:   # before anything below maps into the same units again
+        dump_outputs(args.dump_outputs, rank, timed[-P:])
 
-    # ---- extra: reads already resident in HBM (the round-1 headline) --------
+    # ---- extra (--full): reads already resident in HBM (the round-1 headline) --------
     resident = None
-    if args.resident_steps > 0 and P <= S:
+    if args.full and args.resident_steps > 0 and P <= S:
         us = units[:P]
         for d, u in zip(devs, us):
             rb = batches[u["b"]][0]
@@ -685,7 +738,7 @@ def main():
     # the roofline is rank 0's (only rank 0 prints); the other ranks go straight to the parity gather
     roofline = iso = None
     fatal = []
-    if rank == 0:
+    if rank == 0 and args.full:
         roofline, iso, fatal = roofline_of(args, lib, L, devs, units, batches, P, opts, n_batches, cnt, kb, prof,
                                            timed_slots, chain_ms, per_kernel, ms_per_step, elapsed, world)
     # whole-path algorithmic bytes (SURVEY.md §8d B(read) summed) over the step time
@@ -696,10 +749,10 @@ def main():
 
     # ---- oracle parity on a sample of every rank's timed batches; CPU baseline
     # N=1: ~3,000 reads (the CPU baseline's ~8 s runs come out of it); N>1: 500 per rank
-    n_sample = 0 if args.no_parity else min(args.reads * args.steps, 3000 if world == 1 else 500)
+    n_sample = 0 if args.no_parity or not args.full else min(args.reads * args.steps, 3000 if world == 1 else 500)
     samp = sample_reads(args, batches, timed, n_sample, S, rank)
     gathered = [samp] if world == 1 else [None] * world
-    if world > 1:
+    if world > 1 and n_sample:
         dist.all_gather_object(gathered, samp)
     cpu = parity = None
     if rank == 0 and n_sample:
@@ -715,6 +768,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -750,7 +804,8 @@ def main():
                 "dp_pairs_per_s": dp_pairs_s,
                 "index_build_s": round(t_index, 3), "index_from": index_from, "index_fallback_reason": index_note,
                 "index_upload_s": round(t_up, 3),
-                "mid_occ_device_ms": round(t_mid_dev * 1e3, 2), "mid_occ_host_sort_ms": round(t_mid_host * 1e3, 1),
+                "mid_occ_device_ms": round(t_mid_dev * 1e3, 2),
+                "mid_occ_host_sort_ms": round(t_mid_host * 1e3, 1) if args.full else None,
                 "pack_threads_per_context": pack_thr,
                 "host_ms_per_unit": host_ms,
                 "parity_vs_oracle": parity,

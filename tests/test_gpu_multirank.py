@@ -71,7 +71,7 @@ def test_bench_two_ranks_hg38(tmp_path):
     """bench.py --gpus 2 (the driver's multi-GPU line, self-spawned) on the
     full 3.09 Gb hg38-shaped index, 1,000 x 10 kb reads per rank per step."""
     p = subprocess.run([sys.executable, "-u", "bench.py", "--gpus", "2", "--reads", "1000", "--steps", "2", "--warmup", "1",
-                        "--streams", "2", "--no-cpu"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=840)
+                        "--streams", "2", "--full", "--no-cpu"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=840)
     with open(tmp_path / "bench2.err", "w") as fh:
         fh.write(p.stderr)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -7,7 +7,7 @@ TAG=${1:-ab}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-Q="--no-cpu --no-parity --resident-steps 0 --iso-batches 1"
+Q="--full --no-cpu --no-parity --resident-steps 0 --iso-batches 1"
 IFS='|' read -ra SETS <<< "${AB:?AB=knobs|knobs}"
 for i in $(seq 1 ${N:-5}); do
   for C in ${CFG:-c3}; do

@@ -28,7 +28,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 BARGS=${BARGS:-}
-QUIET="--no-cpu --no-parity --resident-steps 0"
+QUIET="--full --no-cpu --no-parity --resident-steps 0"
 
 line() {   # print the bench line's headline fields
   python3 - "$1" <<'EOF'
@@ -50,18 +50,18 @@ for S in "${STEPS[@]}"; do
     tests:*)
       timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu tests/ -k "${S#tests:}" > "$OUT/gpu_tests_k.log" 2>&1 ;;
     bench)
-      timeout -k 10 600 python -u bench.py $BARGS > "$OUT/bench.json" 2> "$OUT/bench.err"; line "$OUT/bench.json" ;;
+      timeout -k 10 600 python -u bench.py --full $BARGS > "$OUT/bench.json" 2> "$OUT/bench.err"; line "$OUT/bench.json" ;;
     quick)
       timeout -k 10 400 python -u bench.py $QUIET --steps ${N:-16} $BARGS > "$OUT/quick.json" 2> "$OUT/quick.err"; line "$OUT/quick.json" ;;
     c2)
-      timeout -k 10 400 python -u bench.py --preset ecoli --reads 1000 --steps 200 --warmup 2 --no-cpu $BARGS > "$OUT/c2.json" 2> "$OUT/c2.err"; line "$OUT/c2.json" ;;
+      timeout -k 10 400 python -u bench.py --full --preset ecoli --reads 1000 --steps 200 --warmup 2 --no-cpu $BARGS > "$OUT/c2.json" 2> "$OUT/c2.err"; line "$OUT/c2.json" ;;
     c5)
-      timeout -k 10 600 python -u bench.py --reads 2000 --read-len 100000 --steps 12 --warmup 1 --no-cpu $BARGS > "$OUT/c5.json" 2> "$OUT/c5.err"; line "$OUT/c5.json" ;;
+      timeout -k 10 600 python -u bench.py --full --reads 2000 --read-len 100000 --steps 12 --warmup 1 --no-cpu $BARGS > "$OUT/c5.json" 2> "$OUT/c5.err"; line "$OUT/c5.json" ;;
     multi)
       rc=0; timeout -k 10 120 python -u bench.py --gpus 2 --steps 2 > "$OUT/multi_nccl2.json" 2> "$OUT/multi_nccl2.err" || rc=$?
       echo "bench.py --gpus 2 on $(python3 -c 'import torch; print(torch.cuda.device_count())') GPU(s): exit $rc" | tee "$OUT/multi_nccl2.rc"
       [ "$rc" -ne 0 ] || { echo "expected a loud failure"; exit 1; }
-      MM2G_DIST_BACKEND=gloo timeout -k 10 900 python -u bench.py --gpus 2 --steps 4 --warmup 1 --streams 2 --no-cpu \
+      MM2G_DIST_BACKEND=gloo timeout -k 10 900 python -u bench.py --full --gpus 2 --steps 4 --warmup 1 --streams 2 --no-cpu \
         > "$OUT/multi_gloo2.json" 2> "$OUT/multi_gloo2.err"; line "$OUT/multi_gloo2.json" ;;
     s1)
       timeout -k 10 400 python -u bench.py $QUIET --steps 6 --warmup 1 --streams 1 --shares 1 $BARGS > "$OUT/s1.json" 2> "$OUT/s1.err"; line "$OUT/s1.json"
