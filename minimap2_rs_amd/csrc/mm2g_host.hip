@@ -72,12 +72,24 @@ static int ensure(DevBuf& b, size_t n, T** out) {
 #define ENSURE(buf, T, n, ptr) do { int e_ = ensure<T>(buf, (n), &(ptr)); if (e_) return e_; } while (0)
 
 struct ProfSlot { std::string name; double ms = 0; int64_t calls = 0; };
-// Batch status block (u64 words, device + pinned copy): [0] BS_* bits | dv
-// overflow, [1] filter-table entries, [2] anchors, [3] minimizers, [4] anchors
-// in the DP, [5] / [6] of them in reads k_chain_seg streams / k_chain_lb runs
-// on, [8 + 3 pass ..] anchors in long (< / >= giant_min) and medium
-// segments of each DP pass (k_lseg_order)
-constexpr int STAT_WORDS = 18;
+// mm2g_batch_counters slots, in the order of api.Device.counters()'s key list
+enum Counter : int {
+    CN_BASES, CN_MINIMIZERS, CN_KEPT_MINIMIZERS, CN_ANCHORS, CN_RESCUED_ANCHORS, CN_DP_PAIRS,
+    CN_DP_ANCHORS,            // anchors left after the sort's singleton filter (the DP input)
+    CN_LONG_ANCHORS, CN_GIANT_ANCHORS, CN_MED_ANCHORS,                        // anchors per chain kernel class, pass 0
+    CN_LONG_ANCHORS_RESCUE, CN_GIANT_ANCHORS_RESCUE, CN_MED_ANCHORS_RESCUE,   // ... and pass 1
+    CN_SEG_STREAM_ANCHORS,    // DP anchors whose keys k_chain_seg streams (pass 0; the rest: sparse items)
+    CN_LB_STREAM_ANCHORS,     // ... that k_chain_lb streams (pass 0; 0 when it did not run)
+    CN_SEG_STREAM_RESCUE,     // rescued anchors whose keys k_chain_seg streams (pass 1)
+    CN_FUSED_ANCHORS,         // anchors of the reads k_sort_read seeds itself (fused seeding)
+    CN_FUSED_MINIMIZERS,      // ... and their minimizers
+    CN_SORT_SMALL_ANCHORS, CN_SORT_CELL_ANCHORS, CN_SORT_WHOLE_ANCHORS,       // anchors per sort class (launch_sort_read)
+    CN_FUSED_BIG_ANCHORS,     // anchors of the reads k_sort_big seeds itself
+    CN_FUSED_BIG_MINIMIZERS,  // ... and their minimizers
+    CN_COUNT
+};
+static_assert(CN_COUNT == MM2G_N_COUNTERS, "counter names and MM2G_N_COUNTERS (include/mm2g.h)");
+static_assert(CN_MED_ANCHORS_RESCUE + 1 - CN_LONG_ANCHORS == ST_CLASSES * ST_PASSES, "one counter per status word from ST_SEG_CLASS on");
 
 // pinned host staging of one read batch (header + nt4 words), double-buffered
 struct Stage { uint64_t* p = nullptr; uint64_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
@@ -227,70 +239,28 @@ struct ProfScope {
     }
 };
 
-// MM2G_KNOB_SORT_PROF: phase times of k_sort_read (wall clock, 100 MHz) to stderr
-static void dump_sort_prof(mm2g_ctx* c, uint64_t* d, uint32_t n) {
-    std::vector<uint64_t> h((size_t)n * 24);
-    if (hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return;
-    (void)hipFree(d);
-    double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot = 0, a0 = 0, a2 = 0, np = 0, nleg = 0, nbigp = 0, ktiny = 0, klong = 0, ksrch = 0;
-    uint64_t t_lo = ~0ULL, t_hi = 0;
-    uint32_t m = 0;
-    std::vector<uint32_t> q0, q2, q3;
-    for (uint32_t r = 0; r < n; ++r) {
-        const uint64_t* p = &h[(size_t)r * 24];
-        if (!p[11]) continue;
-        q3.push_back((uint32_t)p[13]);
-        ++m;
-        for (int k = 0; k < 8; ++k) ph[k] += (double)p[k];
-        tot += (double)(p[11] - p[10]);
-        a0 += (double)p[8]; a2 += (double)(uint32_t)p[9];
-        if ((p[9] >> 32) == 0xffffu) nleg += 1;
-        else if ((p[9] >> 32) == 0xfffeu) nbigp += 1;
-        else np += (double)(p[9] >> 32);
-        t_lo = std::min(t_lo, p[10]); t_hi = std::max(t_hi, p[11]);
-        q0.push_back((uint32_t)p[8]); q2.push_back((uint32_t)p[9]);
-        ktiny += (double)(uint32_t)p[14]; klong += (double)(p[14] >> 32); ksrch += (double)p[15];
-    }
-    if (!m) return;
-    std::sort(q0.begin(), q0.end()); std::sort(q2.begin(), q2.end()); std::sort(q3.begin(), q3.end());
-    auto Q = [](const std::vector<uint32_t>& v, double f) { return v[std::min(v.size() - 1, (size_t)(f * v.size()))]; };
-    fprintf(stderr, "[sort_prof] A0 q10/50/90/99/max=%u/%u/%u/%u/%u  A q10/50/90/99/max=%u/%u/%u/%u/%u  kept cells q10/50/90/99/max=%u/%u/%u/%u/%u\n",
-            Q(q0, .1), Q(q0, .5), Q(q0, .9), Q(q0, .99), q0.back(), Q(q2, .1), Q(q2, .5), Q(q2, .9), Q(q2, .99), q2.back(),
-            Q(q3, .1), Q(q3, .5), Q(q3, .9), Q(q3, .99), q3.back());
-    fprintf(stderr, "[sort_prof] reads=%u (whole-read radix %.0f, bucket path %.0f) A0=%.0f A=%.0f nbig=%.2f windows=%.2f us/read: p1+kc=%.1f p2=%.1f gather=%.1f fuse_stage=%.1f chunk=%.1f rank=%.1f p4b/radix=%.1f total=%.1f span_us=%.1f concurrency=%.1f\n",
-            m, nleg, nbigp, a0 / m, a2 / m, np / m, ph[7] / m, ph[0] / m / 100, ph[1] / m / 100, ph[2] / m / 100, ph[3] / m / 100, ph[4] / m / 100,
-            ph[5] / m / 100, ph[6] / m / 100, tot / m / 100, (double)(t_hi - t_lo) / 100, tot / (double)(t_hi - t_lo));
-    fprintf(stderr, "[sort_prof] keys per read in segments <= %u: %.0f, 17..64: %.0f, > 64: %.0f (%.2f other-chunk searches each)\n",
-            16u, ktiny / m, (a2 - ktiny - klong) / m, klong / m, klong > 0 ? ksrch / klong : 0.0);
-}
-
-// MM2G_SKETCH_PROF: phase times of k_sketch summed over each read's tiles
-static void dump_sketch_prof(mm2g_ctx* c, uint64_t* d, uint32_t n) {
-    std::vector<uint64_t> h((size_t)n * 8);
-    if (hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) return;
-    (void)hipFree(d);
-    double ph[5] = {0, 0, 0, 0, 0}, L = 0;
-    uint32_t m = 0;
-    uint64_t t_hi = 0, tiles = 0, slow = 0;
-    for (uint32_t r = 0; r < n; ++r) {
-        const uint64_t* p = &h[(size_t)r * 8];
-        if (!p[5]) continue;
-        ++m;
-        tiles += p[7] >> 32; slow += p[7] & 0xffffffffULL;
-        for (int k = 0; k < 5; ++k) ph[k] += (double)p[k];
-        L += (double)p[5];
-        t_hi = std::max(t_hi, p[6]);
-    }
-    if (!m) return;
-    double tot = ph[0] + ph[1] + ph[2] + ph[3] + ph[4];
-    fprintf(stderr, "[sketch_prof] reads=%u len=%.0f us/read: stage=%.1f warmup=%.1f phase1=%.1f phase2=%.1f tail=%.1f total=%.1f; exact-path tiles %.1f%%\n",
-            m, L / m, ph[0] / m / 100, ph[1] / m / 100, ph[2] / m / 100, ph[3] / m / 100, ph[4] / m / 100, tot / m / 100,
-            tiles ? 100.0 * (double)slow / (double)tiles : 0.0);
-}
+// profiling dumps to stderr (the end of this file)
+static void dump_sort_prof(mm2g_ctx* c, uint64_t* d, uint32_t n);
+static void dump_sketch_prof(mm2g_ctx* c, uint64_t* d, uint32_t n);
+static int chain_prof_begin(mm2g_ctx* c, ChainArgs& ca);
+static int dump_chain_prof(mm2g_ctx* c, int pass, ChainArgs& ca);
 
 static inline uint32_t bit_width(uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1; } return b; }
+// The anchor key layout (mm2g_internal.h) for query positions <= max_q, reference positions <= max_p
+static int make_key_layout(uint64_t max_q, uint64_t max_p, uint32_t n_seq, KeyLayout& kl) {
+    kl.n_seq = n_seq;
+    kl.qb = std::max<uint32_t>(1, bit_width(max_q));
+    kl.rb = std::max<uint32_t>(1, bit_width(max_p));
+    kl.gb = std::max<uint32_t>(1, bit_width(2ull * n_seq));
+    if (kl.qb + kl.rb + kl.gb > 64) return set_err(MM2G_E_UNSUP, "anchor key needs %u bits (> 64)", kl.qb + kl.rb + kl.gb);
+    return 0;
+}
+// A key's group -> (rid, rev): forward, reverse, the Q19 pseudo-group 2 * n_seq
+static inline void group_to_rid_rev(uint32_t g, uint32_t n_seq, int32_t& rid, int32_t& rev) {
+    if (g == 2u * n_seq) { rid = 0x7fffffff; rev = 1; }
+    else if (g >= n_seq) { rid = (int32_t)(g - n_seq); rev = 1; }
+    else { rid = (int32_t)g; rev = 0; }
+}
 static inline int grid_for(uint32_t n) { int b = (int)((n + 3) / 4); return std::max(1, std::min(b, 4096)); }
 
 template <size_t N>
@@ -788,7 +758,9 @@ static int run_sketch(mm2g_ctx* c, int w, int k, SketchBufs& B, int32_t* ovf, Re
         if (zout) HIPCHK(hipMemsetAsync(zout, 0, sizeof(ReadOut) * ((size_t)n + 1), c->stream));
         if (zst) HIPCHK(hipMemsetAsync(zst, 0, STAT_WORDS * 8, c->stream));
     }
-    SketchArgs a{nullptr, c->d_rd_off, n, w, k, base, end, x, y, cnt, ovf};
+    SketchArgs a{};
+    a.rd_off = c->d_rd_off; a.n = n; a.w = w; a.k = k;
+    a.out_base = base; a.out_end = end; a.mz_x = x; a.mz_y = y; a.mz_cnt = cnt; a.overflow = ovf;
     a.x64 = c->knob[MM2G_KNOB_SKETCH_X32] ? 0u : 1u;
     a.pk_words = c->d_words; a.pk_off = c->d_pk_off; a.amb_off = c->d_amb_off; a.mz_need = need;
     if (views) {
@@ -898,14 +870,41 @@ static int check_opts(mm2g_ctx* c, const mm2g_map_opts* o, int32_t& mdx0, int32_
 // over the sorted keys of the batch (cnt2/smax: the sort's singleton filter).
 // full: exact f/pprev for every anchor (debug mode, mm2g_chain_batch with DP
 // arrays requested): no segment pruning, no lazy windows.
-static int run_chain(mm2g_ctx* c, uint32_t n, const uint64_t* rd_off, const ChainKParams& P0, float gap, int npass, int32_t mdx1,
-                     int32_t mdy1, int32_t bw_long, uint64_t A_cap, const uint64_t* a_off, const uint32_t* a_cnt, uint64_t* keys,
-                     uint64_t* ktmp, const uint32_t* cnt2, const uint64_t* smax, ReadOut* out, const uint32_t* abort, bool full,
-                     unsigned long long* stat = nullptr, bool order_ready = false, const uint32_t* sum_mz = nullptr) {
+struct ChainJob {
+    uint32_t n = 0;
+    const uint64_t* rd_off = nullptr;      // read offsets (qlen = their difference)
+    const uint64_t* a_off = nullptr;       // anchor offsets; a_cnt: the per-read counts the read order is made from
+    const uint32_t* a_cnt = nullptr;
+    uint64_t *keys = nullptr, *ktmp = nullptr;   // sorted keys; the other buffer receives the chains
+    const uint32_t* cnt2 = nullptr; const uint64_t* smax = nullptr;
+    ReadOut* out = nullptr;
+    const uint32_t* abort = nullptr;       // the batch status word (null: none)
+    unsigned long long* stat = nullptr;    // the status block the counters go to (null: none)
+    ChainKParams P0{};                     // pass 0; the rescue pass (npass 2) runs under mdx1, mdy1, bw_long
+    float gap = 0;                         // chn_pen_gap
+    int npass = 1;
+    int32_t mdx1 = 0, mdy1 = 0, bw_long = 0;
+    uint64_t A_cap = 0;                    // anchors the workspaces hold
+    bool full = false;
+    bool order_ready = false;              // c->order already holds the heaviest-first order of these reads
+    const uint32_t* sum_mz = nullptr;      // mz_cnt: with stat, the last pass's k_seg_items also writes the batch sums
+};
+// run_chain's kernel arguments and the buffers its passes switch between
+struct ChainWork {
+    ChainArgs ca{};
+    int32_t* fmin = nullptr;               // per-read lower bounds (null: no pruning)
+    uint64_t* isob = nullptr;              // pass 0's segment-start words, with the candidate queue sq / sq_n
+    uint2* sq = nullptr; uint32_t* sq_n = nullptr; uint32_t sq_cap = 0;
+};
+// The DP workspaces, the read order and the pass-independent kernel arguments
+static int chain_setup(mm2g_ctx* c, const ChainJob& J, ChainWork& W) {
+    const uint32_t n = J.n;
+    const uint64_t A_cap = J.A_cap;
+    ChainArgs& ca = W.ca;
     int32_t *fb, *pb;
     ENSURE(c->fbuf, int32_t, A_cap, fb); ENSURE(c->ppbuf, int32_t, A_cap, pb);
     int16_t* lut; uint32_t* work;
-    if (int e = upload_lut(c, gap, std::max(P0.bw, npass > 1 ? bw_long : 0) + 1, &lut)) return e;
+    if (int e = upload_lut(c, J.gap, std::max(J.P0.bw, J.npass > 1 ? J.bw_long : 0) + 1, &lut)) return e;
     ENSURE(c->work, uint32_t, 4, work);
     // work: [0..1] k_chain_giant hand-out per pass (k_seg_items of pass 0 clears it)
     uint32_t* order;
@@ -922,181 +921,145 @@ static int run_chain(mm2g_ctx* c, uint32_t n, const uint64_t* rd_off, const Chai
     const uint32_t mcap2 = (uint32_t)std::min<uint64_t>(A_cap / (CHAIN_TINY + 1) + 64, 0xffffffffu);
     uint4* mseg;
     ENSURE(c->mseg, uint4, mcap2, mseg);
-    if (!order_ready) LCHK(launch_read_order(n, a_cnt, order, c->stream));   // map_enqueue made the same order
+    if (!J.order_ready) LCHK(launch_read_order(n, J.a_cnt, order, c->stream));   // map_enqueue made the same order
     const int64_t* K = c->knob;
-    const bool lazy = (!full && K[MM2G_KNOB_LAZY]) || K[MM2G_KNOB_LAZY] == 2;   // 2: also with full DP arrays (tests)
-    ChainArgs ca{n, rd_off, a_off, keys, fb, pb, (uint32_t*)ktmp, lut, P0, c->kl, out, work,
-                 std::min(c->keys.cap, c->fbuf.cap / 4 * 8) / 8, nullptr, order, A_cap, std::min<int32_t>((int32_t)n, 4 * 256), tmark,
-                 lseg, lseg_n, lcap, lseg_order, rbest, cnt2, smax, mseg, lseg_n + 2, lseg_n + 3, mcap2, nullptr, 0u,
-                 lazy ? 1u : 0u, nullptr, 0u};
-    ca.abort = abort;
-    ca.full_dp = full ? 1u : 0u;   // not "no fmin": with pruning off, production still follows the med_pairs knobs
-    int32_t* fmin_buf = nullptr;
-    if (!full && K[MM2G_KNOB_PRUNE]) ENSURE(c->fmin, int32_t, n, fmin_buf);
+    const bool lazy = (!J.full && K[MM2G_KNOB_LAZY]) || K[MM2G_KNOB_LAZY] == 2;   // 2: also with full DP arrays (tests)
+    ca.n = n; ca.rd_off = J.rd_off; ca.a_off = J.a_off; ca.keys = J.keys;
+    ca.f = fb; ca.pp = pb; ca.chain = (uint32_t*)J.ktmp; ca.lut = lut;
+    ca.P = J.P0; ca.kl = c->kl; ca.out = J.out; ca.work = work;
+    ca.cap_keys = std::min(c->keys.cap, c->fbuf.cap / 4 * 8) / 8;
+    ca.order = order; ca.a_total = A_cap; ca.n_prio = std::min<int32_t>((int32_t)n, 4 * 256); ca.tmark = tmark;
+    ca.lseg = lseg; ca.lseg_n = lseg_n; ca.lseg_cap = lcap; ca.lseg_order = lseg_order; ca.rbest = rbest;
+    ca.cnt2 = J.cnt2; ca.smax = J.smax;
+    // lseg_n's four counters: long-segment queue length of pass 0 / pass 1, medium queue length, its hand-out
+    ca.mseg = mseg; ca.mseg_n = lseg_n + 2; ca.mseg_take = lseg_n + 3; ca.mseg_cap = mcap2;
+    ca.lazy = lazy ? 1u : 0u;
+    ca.abort = J.abort;
+    ca.full_dp = J.full ? 1u : 0u;   // not "no fmin": with pruning off, production still follows the med_pairs knobs
+    if (!J.full && K[MM2G_KNOB_PRUNE]) ENSURE(c->fmin, int32_t, n, W.fmin);
     // pass 0's segment-start words (k_chain_lb -> k_chain_seg's sparse items): read r at (a_off[r] >> 6) + r
-    uint64_t* isob = nullptr;
-    uint2* sq = nullptr;
-    uint32_t* sq_n = nullptr;
-    const uint32_t sq_cap = (uint32_t)std::min<uint64_t>(A_cap / 64 + n + 16, 0xffffffffu);
-    if (fmin_buf && K[MM2G_KNOB_SEG_SPARSE] && K[MM2G_KNOB_MED_PAIRS] == 0) {
-        ENSURE(c->isob, uint64_t, A_cap / 64 + n + 2, isob);
-        ENSURE(c->sq, uint2, sq_cap, sq);
-        ENSURE(c->sq_n, uint32_t, 1, sq_n);
+    W.sq_cap = (uint32_t)std::min<uint64_t>(A_cap / 64 + n + 16, 0xffffffffu);
+    if (W.fmin && K[MM2G_KNOB_SEG_SPARSE] && K[MM2G_KNOB_MED_PAIRS] == 0) {
+        ENSURE(c->isob, uint64_t, A_cap / 64 + n + 2, W.isob);
+        ENSURE(c->sq, uint2, W.sq_cap, W.sq);
+        ENSURE(c->sq_n, uint32_t, 1, W.sq_n);
     }
-    uint32_t* item_off;
-    ENSURE(c->item_off, uint32_t, n + 1, item_off);
-    ca.item_off = item_off;
+    ENSURE(c->item_off, uint32_t, n + 1, ca.item_off);
     {   // items per read <= max(ceil(A / seg_chunk), the sort's candidate budget A / 32 + 8)
         const uint64_t icap = std::min<uint64_t>(A_cap / 32 + 8ull * n + 1024, 0xffffffffull);
-        uint32_t* ir;
-        ENSURE(c->item_read, uint32_t, icap, ir);
-        ca.item_read = ir; ca.item_cap = (uint32_t)icap;
+        ENSURE(c->item_read, uint32_t, icap, ca.item_read);
+        ca.item_cap = (uint32_t)icap;
     }
     ca.seg_chunk = std::max<uint32_t>(64u, (uint32_t)K[MM2G_KNOB_SEG_CHUNK] & ~63u);
     ca.spec_rounds = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(16, K[MM2G_KNOB_SPEC_ROUNDS]));
     ca.spec_eval = K[MM2G_KNOB_SPEC_EVAL] ? 1u : 0u;
     ca.spec_batch = K[MM2G_KNOB_SPEC_BATCH] == 8 ? 8u : 4u;
     ca.cands_longw = K[MM2G_KNOB_CANDS_LONGW] > 0 ? (uint32_t)std::min<int64_t>(K[MM2G_KNOB_CANDS_LONGW], 0x7fffffff) : 0x7fffffffu;
+    return 0;
+}
+
+// One DP pass: pass 0, or the rescue of the reads it flagged
+// One kernel of a pass under its profile slot
+static int chain_launch(mm2g_ctx* c, const char* slot, ChainStage stage, const ChainArgs& ca, int blocks) {
+    ProfScope ps(c, slot);
+    LCHK(launch_chain_stage(stage, ca, blocks, c->stream));
+    return 0;
+}
+
+static int chain_pass(mm2g_ctx* c, const ChainJob& J, ChainWork& W, int pass) {
+    const uint32_t n = J.n;
+    const int64_t* K = c->knob;
+    unsigned long long* const stat = J.stat;
+    ChainArgs& ca = W.ca;
+    if (pass == 1) {
+        ca.P.pass = 1; ca.P.bw = J.bw_long; ca.P.max_dist_x = J.mdx1; ca.P.max_dist_y = J.mdy1;
+        ca.P.lut_n = J.bw_long + 1; ca.lseg_n = (uint32_t*)c->lseg_n.p + 1;   // its own queue length
+    }
+    int sb = chain_max_blocks(ca.P.lut_n, ChainStage::Seg), lb = chain_max_blocks(ca.P.lut_n, ChainStage::Long),
+        mb = chain_max_blocks(ca.P.lut_n, ChainStage::Med);
+    if (sb <= 0) sb = 1024;
+    if (lb <= 0) lb = 1024;
+    if (mb <= 0) mb = 1024;
+    sb = std::max(1, std::min((int)((n * 4 + 3) / 4), sb));   // items: up to ~4 chunks per read
+    // Lower bound of each read's best f (k_chain_lb, this pass's parameters): prunes
+    // segments (not in debug mode).  In the rescue pass (rescued reads only) the bound
+    // is LB_1, raised by pass 0's LB_0 when the rescue's comput_sc limits are all at
+    // least pass 0's (bw_long >= bw, max_dist_x/y no smaller): every pass-0 transition
+    // is then accepted there with the same score, so its best f >= LB_0.  The reference
+    // accepts -r A,B with B < A (main.rs:205-206): then pass-0 steps with dd in
+    // (bw_long, bw] are rejected in the rescue and LB_0 does not bound it.
+    const bool rescue_wider = J.bw_long >= J.P0.bw && J.mdx1 >= J.P0.max_dist_x && J.mdy1 >= J.P0.max_dist_y;
+    ca.fmin = (pass == 0 || K[MM2G_KNOB_PRUNE_RESCUE]) ? W.fmin : nullptr;
+    if (pass == 0) c->lb_ran0 = ca.fmin != nullptr;
+    ca.isob = W.isob;
+    ca.seg_streamed = stat ? stat + ST_SEG_STREAMED + pass : nullptr;
+    ca.zero_fmin = ca.fmin && (pass == 0 || !rescue_wider) ? 1u : 0u;   // cleared by k_seg_items
+    ca.sq = nullptr; ca.sq_cap = 0;
+    ca.sq_n = (ca.fmin && W.isob) ? W.sq_n : nullptr;                      // ... as is the item counter
+    // the last pass's k_seg_items also writes the batch sums (ST_MINIMIZERS, ST_DP_ANCHORS): one launch less
+    ca.bsum = (J.sum_mz && stat && pass == J.npass - 1) ? stat : nullptr;
+    ca.mz_cnt = J.sum_mz;
+    if (int e = chain_launch(c, pass ? "chain_items_rescue" : "chain_items", ChainStage::Items, ca, 1)) return e;
+    if (ca.fmin) {
+        if (int e = chain_launch(c, pass ? "chain_lb_rescue" : "chain_lb", ChainStage::Lb, ca, 2048)) return e;
+        if (ca.isob) {   // candidate segments per read; k_chain_seg streams only the reads left over
+            ca.sq = W.sq; ca.sq_cap = W.sq_cap;
+            ProfScope ps(c, pass ? "chain_cands_rescue" : "chain_cands");
+            // one workgroup per 16 reads; with long reads (over ~64 kb) also one per read (up to
+            // 1024), since each such read takes a whole workgroup
+            // (the kernel's criterion, cnt2 > cands_longw * 64: at most A_cap / (64 cands_longw) such reads)
+            const uint64_t nlong = std::min<uint64_t>(n, J.A_cap / (64ull * ca.cands_longw) + 1);
+            const uint32_t cb = std::max<uint32_t>((n + 15) / 16, (uint32_t)nlong);
+            LCHK(launch_chain_stage(ChainStage::Cands, ca, (int)std::min<uint32_t>(cb, 1024), c->stream));
+        }
+    }
+    if (int e = chain_prof_begin(c, ca)) return e;   // MM2G_KNOB_LSEG_PROF: ca.lseg_prof, ca.gprof
+    ca.seg_stat = stat ? stat + ST_SEG_CLASS + ST_CLASSES * pass : nullptr;
     // Giant segments (k_chain_giant): the rescue pass's pseudo-group clusters
     // settle in a few no-break policy-iteration rounds.  Pass 0's long segments
     // are real chains whose windows carry many mark sources: k_chain_long is
     // faster on the usual few-hundred-anchor ones; its
     // exact mode is off by default (measured 15x (C3) and 6x (C5) slower).
-    uint32_t giant_min[2] = {K[MM2G_KNOB_GIANT_MIN0] > 0 ? (uint32_t)std::max<int64_t>(2, K[MM2G_KNOB_GIANT_MIN0]) : 0xffffffffu,
-                             (uint32_t)std::max<int64_t>(2, K[MM2G_KNOB_GIANT_MIN])};
-    for (int pass = 0; pass < npass; ++pass) {
-        if (pass == 1) {
-            ca.P.pass = 1; ca.P.bw = bw_long; ca.P.max_dist_x = mdx1; ca.P.max_dist_y = mdy1;
-            ca.P.lut_n = bw_long + 1; ca.lseg_n = lseg_n + 1;
-        }
-        int sb = chain_max_blocks(ca.P.lut_n, 0), lb = chain_max_blocks(ca.P.lut_n, 1), mb = chain_max_blocks(ca.P.lut_n, 2);
-        if (sb <= 0) sb = 1024;
-        if (lb <= 0) lb = 1024;
-        if (mb <= 0) mb = 1024;
-        sb = std::max(1, std::min((int)((n * 4 + 3) / 4), sb));   // items: up to ~4 chunks per read
-        static const char* names[2][5] = {{"chain_seg", "chain_med", "chain_lorder", "chain_long", "chain_fin"},
-                                          {"chain_seg_rescue", "chain_med_rescue", "chain_lorder_rescue", "chain_long_rescue", "chain_fin_rescue"}};
-        const int blocks[5] = {sb, mb, 1, lb, 0};
-        // Lower bound of each read's best f (k_chain_lb, this pass's parameters): prunes
-        // segments (not in debug mode).  In the rescue pass (rescued reads only) the bound
-        // is LB_1, raised by pass 0's LB_0 when the rescue's comput_sc limits are all at
-        // least pass 0's (bw_long >= bw, max_dist_x/y no smaller): every pass-0 transition
-        // is then accepted there with the same score, so its best f >= LB_0.  The reference
-        // accepts -r A,B with B < A (main.rs:205-206): then pass-0 steps with dd in
-        // (bw_long, bw] are rejected in the rescue and LB_0 does not bound it.
-        const bool rescue_wider = bw_long >= P0.bw && mdx1 >= P0.max_dist_x && mdy1 >= P0.max_dist_y;
-        ca.fmin = (pass == 0 || K[MM2G_KNOB_PRUNE_RESCUE]) ? fmin_buf : nullptr;
-        if (pass == 0) c->lb_ran0 = ca.fmin != nullptr;
-        ca.isob = isob;
-        ca.seg_streamed = stat ? stat + 5 + pass : nullptr;   // status words 5 / 6
-        ca.zero_fmin = ca.fmin && (pass == 0 || !rescue_wider) ? 1u : 0u;   // cleared by k_seg_items
-        ca.sq = nullptr; ca.sq_cap = 0;
-        ca.sq_n = (ca.fmin && isob) ? sq_n : nullptr;                      // ... as is the item counter
-        // the last pass's k_seg_items also writes the batch sums (status words 3 and 4): one launch less
-        ca.bsum = (sum_mz && stat && pass == npass - 1) ? stat : nullptr;
-        ca.mz_cnt = sum_mz;
-        {
-            ProfScope ps(c, pass ? "chain_items_rescue" : "chain_items");
-            LCHK(launch_chain_stage(6, ca, 1, c->stream));
-        }
-        if (ca.fmin) {
-            {
-                ProfScope ps(c, pass ? "chain_lb_rescue" : "chain_lb");
-                LCHK(launch_chain_stage(5, ca, 2048, c->stream));
-            }
-            if (ca.isob) {   // candidate segments per read; k_chain_seg streams only the reads left over
-                ca.sq = sq; ca.sq_cap = sq_cap;
-                ProfScope ps(c, pass ? "chain_cands_rescue" : "chain_cands");
-                // one workgroup per 16 reads; with long reads (over ~64 kb) also one per read (up to
-                // 1024), since each such read takes a whole workgroup
-                // (the kernel's criterion, cnt2 > cands_longw * 64: at most A_cap / (64 cands_longw) such reads)
-                const uint64_t nlong = std::min<uint64_t>(n, A_cap / (64ull * ca.cands_longw) + 1);
-                const uint32_t cb = std::max<uint32_t>((n + 15) / 16, (uint32_t)nlong);
-                LCHK(launch_chain_stage(10, ca, (int)std::min<uint32_t>(cb, 1024), c->stream));
-            }
-        }
-        ca.lseg_prof = K[MM2G_KNOB_LSEG_PROF] ? 1u : 0u;
-        unsigned long long* gprof = nullptr;
-        if (ca.lseg_prof) {
-            HIPCHK(hipMalloc(&gprof, 32 * 8));
-            HIPCHK(hipMemsetAsync(gprof, 0, 32 * 8, c->stream));
-        }
-        ca.gprof = gprof;
-        ca.seg_stat = stat ? stat + 8 + 3 * pass : nullptr;
-        for (int stg = 0; stg < 5; ++stg) {
-            ca.giant_min = giant_min[pass];
-            ca.giant_exact = pass == 0 ? 1u : 0u;
-            ca.est_lane = (int32_t)std::max<int64_t>(0, std::min<int64_t>(1 << 20, K[pass ? MM2G_KNOB_MED_PAIRS_RESCUE : MM2G_KNOB_MED_PAIRS]));
-            if (stg == 2) {   // longest-first order of the long segments (k_chain_giant and k_chain_long)
-                ProfScope ps(c, names[pass][stg]);
-                LCHK(launch_chain_stage(2, ca, 1, c->stream));
-            }
-            // production only; the pin bitmap and the lo field bound the window (max_iter <= 5120)
-            if (stg == 2 && ca.lazy && ca.giant_min != 0xffffffffu && ca.P.max_iter <= 5120 && K[MM2G_KNOB_GIANT]) {
-                ProfScope ps(c, pass ? "chain_giant_rescue" : "chain_giant");
-                if (K[MM2G_KNOB_GIANT_LCAP] > 0) ca.giant_lcap = (uint32_t)std::max<int64_t>(16, K[MM2G_KNOB_GIANT_LCAP]) & ~15u;
-                LCHK(launch_chain_stage(7, ca, 0, c->stream));   // workgroups: as many as fit (giant_lcap sets their LDS)
-                // longer segments from a per-workgroup HBM slice (100 kb reads' rescue)
-                const uint32_t gmax = (uint32_t)std::max<int64_t>(0, K[MM2G_KNOB_GIANT_GMAX]) & ~15u;
-                if (gmax) {
-                    const int gblocks = (int)std::max<int64_t>(1, K[MM2G_KNOB_GIANT_GBLOCKS]);
-                    unsigned char* scr;
-                    ENSURE(c->giant_scr, unsigned char, (size_t)gblocks * gmax * 42, scr);
-                    ca.giant_scr = scr;
-                    ca.giant_gmax = gmax;
-                    LCHK(launch_chain_stage(8, ca, gblocks, c->stream));
-                }
-            }
-            if (stg == 2) continue;   // launched above
-            // k_chain_seg routes a segment to k_chain_med only when its estimated pairs stay
-            // under est_lane (EST_LANE for pass 0 with full DP arrays): at 0 the queue stays
-            // empty and the launch would only add its latency (C2 is launch-bound)
-            if (stg == 1 && ca.est_lane == 0 && !(pass == 0 && full)) continue;
-            ProfScope ps(c, names[pass][stg]);
-            LCHK(launch_chain_stage(stg, ca, blocks[stg], c->stream));
-        }
-        if (gprof) {   // k_chain_giant phase sums (wall clock, 100 MHz); k_chain_long per-anchor cycles
-            unsigned long long g[32];
-            HIPCHK(hipMemcpyAsync(g, gprof, sizeof g, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            (void)hipFree(gprof);
-            ca.gprof = nullptr;
-            fprintf(stderr, "[giant_prof] pass %d: %llu segments, %llu anchors, %llu iterations, %llu pins, %llu fallbacks; block-us: total %.0f "
-                            "setup %.0f eval %.0f changed %.0f improve %.0f children %.0f markcheck %.0f pin %.0f write %.0f\n",
-                    pass, g[8], g[9], g[10], g[11], g[13], g[12] / 100.0, g[0] / 100.0, g[1] / 100.0, g[2] / 100.0, g[3] / 100.0,
-                    g[4] / 100.0, g[5] / 100.0, g[6] / 100.0, g[7] / 100.0);
-            const double np_ = (double)std::max<unsigned long long>(g[17] + g[19], 1);
-            fprintf(stderr, "[long_prof] pass %d: %llu anchors in long segments, %llu committed by the speculative block pass in %llu rounds; "
-                            "per-anchor path: %llu settled by the simple/shortcut step, %llu exact (%llu 64-lane window steps in all); "
-                            "shader cycles per per-anchor-path anchor: st %.0f simple %.0f exact %.0f tail %.0f\n",
-                    pass, g[16], g[24], g[25], g[17], g[19], g[18], g[20] / np_, g[21] / np_, g[22] / np_, g[23] / np_);
-            fprintf(stderr, "[long_prof] pass %d heaviest segment: %llu anchors committed speculatively in %llu rounds, %llu by the per-anchor path; "
-                            "shader cycles: speculative %llu, per-anchor path %llu, segment %llu\n",
-                    pass, g[26], g[27], g[28], g[30], g[29], g[31]);
-        }
-        if (ca.lseg_prof) {   // the slowest long segments of this pass
-            uint32_t nl = 0;
-            HIPCHK(hipMemcpyAsync(&nl, ca.lseg_n, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            nl = std::min(nl, lcap);
-            std::vector<uint4> ls(nl);
-            if (nl) HIPCHK(hipMemcpy(ls.data(), lseg, (size_t)nl * 16, hipMemcpyDeviceToHost));
-            // lseg[].w: wall-clock ticks (100 MHz) of the kernel that ran the segment; bit 31 = k_chain_giant's
-            const uint32_t GBIT = 0x80000000u;
-            std::sort(ls.begin(), ls.end(), [&](const uint4& x, const uint4& y) { return (x.w & ~GBIT) > (y.w & ~GBIT); });
-            double tot = 0, tot_g = 0; uint32_t ng = 0;
-            for (auto& v : ls) { tot += v.w & ~GBIT; if (v.w & GBIT) { tot_g += v.w & ~GBIT; ++ng; } }
-            fprintf(stderr, "[lseg_prof] pass %d: %u long segments (%u by k_chain_giant), sum %.0f us (giant %.0f us); slowest:", pass, nl, ng,
-                    tot / 100, tot_g / 100);
-            for (size_t i = 0; i < ls.size() && i < 8; ++i) {
-                ReadOut ro;
-                HIPCHK(hipMemcpy(&ro, out + ls[i].x, sizeof ro, hipMemcpyDeviceToHost));
-                fprintf(stderr, " (read %u len %u %s %.0f us, read j-steps %u pairs %llu)", ls[i].x, ls[i].z - ls[i].y,
-                        (ls[i].w & GBIT) ? "giant" : "long", (ls[i].w & ~GBIT) / 100.0, ro.n_steps, (unsigned long long)ro.dp_pairs);
-            }
-            fprintf(stderr, "\n");
+    ca.giant_min = pass ? (uint32_t)std::max<int64_t>(2, K[MM2G_KNOB_GIANT_MIN])
+                        : K[MM2G_KNOB_GIANT_MIN0] > 0 ? (uint32_t)std::max<int64_t>(2, K[MM2G_KNOB_GIANT_MIN0]) : 0xffffffffu;
+    ca.giant_exact = pass == 0 ? 1u : 0u;
+    ca.est_lane = (int32_t)std::max<int64_t>(0, std::min<int64_t>(1 << 20, K[pass ? MM2G_KNOB_MED_PAIRS_RESCUE : MM2G_KNOB_MED_PAIRS]));
+    if (int e = chain_launch(c, pass ? "chain_seg_rescue" : "chain_seg", ChainStage::Seg, ca, sb)) return e;
+    // k_chain_seg routes a segment to k_chain_med only when its estimated pairs stay
+    // under est_lane (EST_LANE for pass 0 with full DP arrays): at 0 the queue stays
+    // empty and the launch would only add its latency (C2 is launch-bound)
+    if (!(ca.est_lane == 0 && !(pass == 0 && J.full)))
+        if (int e = chain_launch(c, pass ? "chain_med_rescue" : "chain_med", ChainStage::Med, ca, mb)) return e;
+    // longest-first order of the long segments (k_chain_giant and k_chain_long)
+    if (int e = chain_launch(c, pass ? "chain_lorder_rescue" : "chain_lorder", ChainStage::LsegOrder, ca, 1)) return e;
+    // production only; the pin bitmap and the lo field bound the window (max_iter <= 5120)
+    if (ca.lazy && ca.giant_min != 0xffffffffu && ca.P.max_iter <= 5120 && K[MM2G_KNOB_GIANT]) {
+        ProfScope ps(c, pass ? "chain_giant_rescue" : "chain_giant");
+        if (K[MM2G_KNOB_GIANT_LCAP] > 0) ca.giant_lcap = (uint32_t)std::max<int64_t>(16, K[MM2G_KNOB_GIANT_LCAP]) & ~15u;
+        LCHK(launch_chain_stage(ChainStage::Giant, ca, 0, c->stream));   // workgroups: as many as fit (giant_lcap sets their LDS)
+        // longer segments from a per-workgroup HBM slice (100 kb reads' rescue)
+        const uint32_t gmax = (uint32_t)std::max<int64_t>(0, K[MM2G_KNOB_GIANT_GMAX]) & ~15u;
+        if (gmax) {
+            const int gblocks = (int)std::max<int64_t>(1, K[MM2G_KNOB_GIANT_GBLOCKS]);
+            unsigned char* scr;
+            ENSURE(c->giant_scr, unsigned char, (size_t)gblocks * gmax * 42, scr);
+            ca.giant_scr = scr;
+            ca.giant_gmax = gmax;
+            LCHK(launch_chain_stage(ChainStage::GiantHbm, ca, gblocks, c->stream));
         }
     }
+    if (int e = chain_launch(c, pass ? "chain_long_rescue" : "chain_long", ChainStage::Long, ca, lb)) return e;
+    if (int e = chain_launch(c, pass ? "chain_fin_rescue" : "chain_fin", ChainStage::Fin, ca, 0)) return e;
+    if (ca.lseg_prof)
+        if (int e = dump_chain_prof(c, pass, ca)) return e;
+    return 0;
+}
+
+static int run_chain(mm2g_ctx* c, const ChainJob& J) {
+    ChainWork W;
+    if (int e = chain_setup(c, J, W)) return e;
+    for (int pass = 0; pass < J.npass; ++pass)
+        if (int e = chain_pass(c, J, W, pass)) return e;
     return 0;
 }
 
@@ -1132,7 +1095,7 @@ static int reserve_anchor_ws(mm2g_ctx* c, const unsigned long long* st, uint64_t
     }
     (void)hipGetLastError();                  // the failed hipMalloc must not surface as a launch error
     unsigned long long tot = 0;
-    HIPCHK(hipMemcpyAsync(&tot, st + 2, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&tot, st + ST_ANCHORS, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // also: nothing queued still uses the buffers freed below
     const uint64_t need = std::max<uint64_t>((uint64_t)tot, 1);
     for (DevBuf* b : bufs) if (b->cap < need * (b == &c->keys || b == &c->keys_tmp ? 8 : 4)) {
@@ -1144,6 +1107,195 @@ static int reserve_anchor_ws(mm2g_ctx* c, const unsigned long long* st, uint64_t
     const int e = grab(A_cap);
     if (e) (void)hipGetLastError();
     return e;
+}
+
+// What crosses the stages of one map_enqueue (device pointers; each stage fills what it makes).
+struct MapBatch {
+    uint32_t n = 0;
+    KeyLayout kl{};
+    ReadOut* out = nullptr;
+    unsigned long long* st = nullptr;   // the status block (StatWord) ...
+    uint32_t* st32 = nullptr;           // ... and its first word (BS_* bits): the kernels' abort pointer
+    // sketch (sk1)
+    uint64_t mcap = 0;                  // minimizer slots
+    const uint64_t* mz_base = nullptr; const uint32_t* mz_cnt = nullptr; const uint64_t* mz_x = nullptr; const uint32_t* mz_y = nullptr;
+    const uint8_t* keep = nullptr;      // filter
+    // seed count
+    uint32_t *mz_n = nullptr, *mz_poff = nullptr, *a_cnt = nullptr, *a_part = nullptr;
+    uint64_t* a_off = nullptr;
+    uint32_t* rorder = nullptr;         // reads heaviest first
+    uint64_t A_cap = 0;                 // anchors the workspace holds
+    uint64_t *keys = nullptr, *ktmp = nullptr;   // the (sorted, after enqueue_sort) keys and the other buffer
+    // sort
+    bool filt = false;                  // singleton-filter cell path
+    uint32_t sort_small_max = 0, fuse_mmax = 0, fuse_big = 0;
+    uint32_t* cnt2 = nullptr; uint64_t* smax = nullptr;
+};
+
+// 2. query filter (seeds.rs:13-36; (10, 0.01) hard-wired at main.rs:195).  Only
+//    reads whose count table outgrows LDS use the global table; its size is
+//    estimated from the read lengths and checked on the device.
+static int enqueue_filter(mm2g_ctx* c, const mm2g_map_opts* o, MapBatch& B) {
+    const uint32_t n = B.n;
+    {
+        uint64_t est = 0;
+        for (uint32_t r = 0; r < n; ++r) {
+            const uint64_t m = 2 * (c->h_rd_off[r + 1] - c->h_rd_off[r]) / (uint64_t)(o->w + 1) + 64;
+            uint64_t ts = 1;
+            while (ts < 2 * m) ts <<= 1;
+            if (m > 10 && (ts > 4096 || o->k > 16)) est += ts;
+        }
+        c->cap_tab = std::max(c->cap_tab, est);
+        if (c->knob[MM2G_KNOB_WS_MIN] > 0 && !c->redo) c->cap_tab = (uint64_t)c->knob[MM2G_KNOB_WS_MIN];   // tests: force the re-map
+    }
+    uint64_t* tab_off; uint8_t* keep;
+    ENSURE(c->tab_off, uint64_t, n + 1, tab_off);
+    ENSURE(c->keep, uint8_t, B.mcap, keep);
+    {
+        ProfScope ps(c, "scan");
+        LCHK(launch_excl_scan(B.mz_cnt, n, tab_off, 1, 10, o->k, std::max<uint64_t>(c->cap_tab, 1), B.st32, BS_TAB, ST_TAB, c->stream));
+    }
+    FilterArgs fa{};
+    ENSURE(c->tab_key, uint64_t, c->cap_tab, fa.tab_key);
+    ENSURE(c->tab_cnt, uint32_t, c->cap_tab, fa.tab_cnt);
+    fa.n = n; fa.mz_base = B.mz_base; fa.mz_cnt = B.mz_cnt; fa.mz_x = B.mz_x;
+    fa.tab_off = tab_off; fa.keep = keep;
+    fa.q_occ_max = 10; fa.q_occ_frac = 0.01f; fa.cap_tab = c->cap_tab;
+    B.keep = keep;
+    ProfScope ps(c, "filter");
+    LCHK(launch_filter(fa, o->k, grid_for(n), c->stream));
+    return 0;
+}
+
+// k_seed_count's arguments; k_seed_write adds the keys, the read order and the fused-seeding limits
+static SeedArgs seed_args(const mm2g_ctx* c, const mm2g_map_opts* o, const MapBatch& B) {
+    SeedArgs sa{};
+    sa.n = B.n; sa.rd_off = c->d_rd_off;
+    sa.mz_base = B.mz_base; sa.mz_cnt = B.mz_cnt; sa.mz_x = B.mz_x; sa.mz_y = B.mz_y; sa.keep = B.keep;
+    sa.tab = (const IxEntry*)c->dix->tab.p; sa.log2cap = c->log2cap; sa.mid_occ = c->mid_occ;
+    sa.ix_pos = (const uint64_t*)c->dix->ix_pos.p;
+    sa.mz_n = B.mz_n; sa.mz_poff = B.mz_poff; sa.a_cnt = B.a_cnt; sa.a_off = B.a_off;
+    sa.kl = B.kl; sa.span = o->k;
+    sa.cap_pos = c->dix->ix_pos.cap / 8; sa.cap_mz = B.mcap;
+    sa.out = B.out; sa.a_part = B.a_part;
+    sa.abort = B.st32;
+    return sa;
+}
+
+// 3. lookup + anchor count (index.rs:143-154, seeds.rs:42-57), the anchor scan
+//    and the anchor workspace: it keeps its capacity across batches, checked
+//    on the device
+static int enqueue_seed_count(mm2g_ctx* c, const mm2g_map_opts* o, MapBatch& B) {
+    const uint32_t n = B.n;
+    ENSURE(c->mz_n, uint32_t, B.mcap, B.mz_n); ENSURE(c->mz_poff, uint32_t, B.mcap, B.mz_poff);
+    ENSURE(c->a_cnt, uint32_t, n + 1, B.a_cnt); ENSURE(c->a_off, uint64_t, n + 1, B.a_off);
+    ENSURE(c->a_part, uint32_t, (size_t)n * (SEED_PARTS - 1), B.a_part);
+    {
+        const SeedArgs sa = seed_args(c, o, B);
+        ProfScope ps(c, "seed_count");
+        LCHK(launch_seed_count(sa, grid_for(n), c->stream));
+    }
+    if (!c->ws_exact) c->cap_A = std::max<uint64_t>(c->cap_A, 3 * c->total_bases + 65536);   // exact-size mode: see reserve_anchor_ws
+    if (c->knob[MM2G_KNOB_WS_MIN] > 0 && !c->redo) c->cap_A = (uint64_t)c->knob[MM2G_KNOB_WS_MIN];   // tests: force the re-map
+    B.A_cap = c->cap_A;
+    // reads heaviest first (anchor counts from seed_count): the hand-out order of
+    // seed_write, the sort and the chain work items; made by the anchor scan's block
+    ENSURE(c->order, uint32_t, n, B.rorder);
+    {
+        ProfScope ps(c, "scan");
+        LCHK(launch_excl_scan(B.a_cnt, n, B.a_off, 0, 0, o->k, B.A_cap, B.st32, BS_ANCHORS, ST_ANCHORS, c->stream, B.rorder));
+    }
+    if (int e = reserve_anchor_ws(c, B.st, B.A_cap)) return e;
+    B.keys = (uint64_t*)c->keys.p;
+    B.ktmp = (uint64_t*)c->keys_tmp.p;
+    return 0;
+}
+
+// 4. anchors (seeds.rs:62-79) and their sort (seeds.rs:58): k_seed_write, then
+//    the three sorts by read size; the sorted keys end up in B.keys.
+static int enqueue_sort(mm2g_ctx* c, const mm2g_map_opts* o, MapBatch& B) {
+    const uint32_t n = B.n;
+    const int64_t* K = c->knob;
+    SeedArgs sa = seed_args(c, o, B);
+    sa.keys = B.keys; sa.cap_keys = c->keys.cap / 8;
+    sa.order = B.rorder;
+    sa.fuse_mmax = B.fuse_mmax; sa.small_max = B.sort_small_max; sa.fuse_big = B.fuse_big;
+    {
+        ProfScope ps(c, "seed_write");
+        LCHK(launch_seed_write(sa, grid_for(n), c->stream));
+    }
+    uint32_t* rlist;
+    ENSURE(c->cnt2, uint32_t, n, B.cnt2);
+    ENSURE(c->rlist, uint32_t, n + 2, rlist);
+    ENSURE(c->smax, uint64_t, n, B.smax);
+    SortArgs so{};
+    so.n = n; so.a_off = B.a_off; so.keys = B.keys; so.tmp = B.ktmp;
+    so.qb = B.kl.qb; so.rb = B.kl.rb; so.n_seq = B.kl.n_seq;
+    so.cap_keys = c->keys.cap / 8;
+    so.goff = (const uint32_t*)c->dix->goff.p;
+    so.cells = B.filt ? c->dix->cells : 0u;
+    so.cnt2 = B.cnt2; so.smax = B.smax;
+    so.small_max = B.sort_small_max;
+    so.seg_small = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(K[MM2G_KNOB_SEG_SMALL], SEG_THREAD));
+    so.abort = B.st32;
+    so.meta = (uint32_t*)c->fbuf.p;      // the sort's per-key tags live here before the DP needs it
+    so.rlist = rlist; so.rcount = rlist + n; so.rwork = rlist + n + 1;
+    so.order = B.rorder;
+    so.lds_words = (uint32_t)(std::max<int64_t>(0, K[MM2G_KNOB_SORT_LDS_KB]) * 256);
+    so.fuse_mmax = B.fuse_mmax;
+    so.fuse_big = B.fuse_big; so.a_part = B.a_part;
+    so.read_tiny = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(K[MM2G_KNOB_READ_TINY], 1024));
+    so.big_tiny = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(K[MM2G_KNOB_BIG_TINY], 2048));
+    so.small_reg = K[MM2G_KNOB_SMALL_REG] ? 1u : 0u;
+    so.big_wnd = (uint32_t)std::max<int64_t>(0, K[MM2G_KNOB_BIG_WND]);
+    so.rd_off = c->d_rd_off; so.mz_base = B.mz_base; so.mz_cnt = B.mz_cnt; so.mz_y = B.mz_y;
+    so.mz_n = B.mz_n; so.mz_poff = B.mz_poff; so.ix_pos = (const uint64_t*)c->dix->ix_pos.p; so.kl = B.kl; so.span = o->k;
+    so.cap_pos = c->dix->ix_pos.cap / 8;
+    uint64_t* sprof = nullptr;
+    if (K[MM2G_KNOB_SORT_PROF]) { HIPCHK(hipMalloc(&sprof, (size_t)n * 192)); HIPCHK(hipMemsetAsync(sprof, 0, (size_t)n * 192, c->stream)); so.prof = sprof; }
+    if (K[MM2G_KNOB_STOP_AT] == 1) return 0;   // measurement only: no sort
+    {
+        ProfScope ps(c, "sort_small");
+        LCHK(launch_sort_read(SortStage::Small, so, c->stream));
+    }
+    {
+        ProfScope ps(c, "sort_large");
+        LCHK(launch_sort_read(SortStage::Read, so, c->stream));
+    }
+    {
+        ProfScope ps(c, so.cells ? "sort_big" : "sort_radix");   // reads k_sort_read listed: buckets (filter on) or radix
+        LCHK(launch_sort_read(SortStage::Listed, so, c->stream));
+    }
+    if (sprof) dump_sort_prof(c, sprof, n);
+    // the sorted anchors are in the tmp buffer: swap the roles for everything downstream
+    std::swap(c->keys.p, c->keys_tmp.p); std::swap(c->keys.cap, c->keys_tmp.cap);
+    std::swap(B.keys, B.ktmp);
+    return 0;
+}
+
+// 6. dv inputs (paf.rs:156-199): sketch with the INDEX w/k (Q3)
+static int enqueue_dv(mm2g_ctx* c, const mm2g_map_opts* o, const MapBatch& B) {
+    const HostIndex& H = *c->hidx;
+    const bool sep = (H.w != o->w || H.k != o->k);
+    c->dv_separate = sep;
+    if (sep) {
+        if (!(H.w > 0 && H.w < 256 && H.k > 0 && H.k <= 28)) return set_err(MM2G_E_ARG, "index w/k invalid for the dv sketch");
+        if (int e = run_sketch(c, H.w, H.k, c->sk2, (int32_t*)(B.st32 + ST32_DV_OVF))) return e;
+    }
+    SketchBufs& D = sep ? c->sk2 : c->sk1;
+    DvArgs da{};
+    da.n = B.n; da.a_off = B.a_off; da.keys = B.keys; da.chain = (const uint32_t*)B.ktmp;
+    da.mz_base = (const uint64_t*)D.base.p; da.mz_cnt = (const uint32_t*)D.cnt.p; da.mz_y = (const uint32_t*)D.y.p;
+    da.kl = B.kl; da.span = o->k;
+    da.out = B.out;
+    da.cap_keys = c->keys.cap / 8; da.cap_mz = D.y.cap / 4;
+    da.abort = B.st32;
+    da.strict = (H.k & 1) && c->knob[MM2G_KNOB_DV_PAR] ? 1u : 0u;   // odd k: positions strictly increase
+    // reads whose dv sketch outgrows k_dv's 4096 staged positions (~2 per w+1 bases): a workgroup each
+    da.long_m = da.strict && 2ull * c->max_read_len / (uint64_t)(H.w + 1) + 64 > 4096 ? 0xffffffffu : 0u;
+    ProfScope ps(c, "dv");
+    if (c->knob[MM2G_KNOB_STOP_AT] != 4) LCHK(launch_dv(da, c->stream));
+    return 0;
 }
 
 // Queue the whole path for the resident batch on the context stream (no host
@@ -1168,22 +1320,16 @@ static int map_enqueue(mm2g_ctx* c, const mm2g_map_opts* o, bool stop_after_sort
     c->collected = false;
     c->stop_after_sort = stop_after_sort;
     c->last_opts = *o;
-    // key layout
-    KeyLayout kl;
-    kl.n_seq = H.n_seq;
-    kl.qb = std::max<uint32_t>(1, bit_width(c->max_read_len));
-    kl.rb = std::max<uint32_t>(1, bit_width(H.max_len));
-    kl.gb = std::max<uint32_t>(1, bit_width(2ull * H.n_seq));
-    if (kl.qb + kl.rb + kl.gb > 64) return set_err(MM2G_E_UNSUP, "anchor key needs %u bits (> 64)", kl.qb + kl.rb + kl.gb);
-    c->kl = kl;
-    ReadOut* out;
-    ENSURE(c->outb, ReadOut, n + 1, out);
-    unsigned long long* st;
-    ENSURE(c->dstat, unsigned long long, STAT_WORDS, st);
-    uint32_t* st32 = (uint32_t*)st;
+    MapBatch B;
+    B.n = n;
+    if (int e = make_key_layout(c->max_read_len, H.max_len, H.n_seq, B.kl)) return e;
+    c->kl = B.kl;
+    ENSURE(c->outb, ReadOut, n + 1, B.out);
+    ENSURE(c->dstat, unsigned long long, STAT_WORDS, B.st);
+    B.st32 = (uint32_t*)B.st;
     if (n == 0) {
-        HIPCHK(hipMemsetAsync(out, 0, sizeof(ReadOut), c->stream));
-        HIPCHK(hipMemsetAsync(st, 0, STAT_WORDS * 8, c->stream));
+        HIPCHK(hipMemsetAsync(B.out, 0, sizeof(ReadOut), c->stream));
+        HIPCHK(hipMemsetAsync(B.st, 0, STAT_WORDS * 8, c->stream));
     }
     if (c->h_out_cap < (size_t)n + 1) {
         HIPCHK(hipStreamSynchronize(c->stream));   // a previous batch's copy may still target it
@@ -1193,173 +1339,56 @@ static int map_enqueue(mm2g_ctx* c, const mm2g_map_opts* o, bool stop_after_sort
         c->h_out_cap = (size_t)n + 1;
     }
     if (n == 0) {
-        HIPCHK(hipMemcpyAsync(c->h_stat, st, STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_stat, B.st, STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipEventRecord(c->ev_done, c->stream));
         c->mapped = true;
         return 0;
     }
     // 1. sketch (CLI w/k, rid 0: seeds.rs:7-11)
-    if (int e = run_sketch(c, o->w, o->k, c->sk1, (int32_t*)st32, out, st)) return e;   // clears out[] and st[] first
-    const uint64_t mcap = c->sk1.cap;
-    uint64_t* mz_base = (uint64_t*)c->sk1.base.p; uint32_t* mz_cnt = (uint32_t*)c->sk1.cnt.p;
-    // 2. query filter (seeds.rs:13-36; (10, 0.01) hard-wired at main.rs:195).  Only
-    //    reads whose count table outgrows LDS use the global table; its size is
-    //    estimated from the read lengths and checked on the device.
-    {
-        uint64_t est = 0;
-        for (uint32_t r = 0; r < n; ++r) {
-            const uint64_t m = 2 * (c->h_rd_off[r + 1] - c->h_rd_off[r]) / (uint64_t)(o->w + 1) + 64;
-            uint64_t ts = 1;
-            while (ts < 2 * m) ts <<= 1;
-            if (m > 10 && (ts > 4096 || o->k > 16)) est += ts;
-        }
-        c->cap_tab = std::max(c->cap_tab, est);
-        if (c->knob[MM2G_KNOB_WS_MIN] > 0 && !c->redo) c->cap_tab = (uint64_t)c->knob[MM2G_KNOB_WS_MIN];   // tests: force the re-map
-    }
-    uint64_t* tab_off; uint8_t* keep;
-    ENSURE(c->tab_off, uint64_t, n + 1, tab_off);
-    ENSURE(c->keep, uint8_t, mcap, keep);
-    {
-        ProfScope ps(c, "scan");
-        LCHK(launch_excl_scan(mz_cnt, n, tab_off, 1, 10, o->k, std::max<uint64_t>(c->cap_tab, 1), st32, BS_TAB, 1, c->stream));
-    }
-    uint64_t* tkey; uint32_t* tcnt;
-    ENSURE(c->tab_key, uint64_t, c->cap_tab, tkey);
-    ENSURE(c->tab_cnt, uint32_t, c->cap_tab, tcnt);
-    {
-        FilterArgs fa{n, mz_base, mz_cnt, (const uint64_t*)c->sk1.x.p, tab_off, tkey, tcnt, keep, 10, 0.01f, c->cap_tab};
-        ProfScope ps(c, "filter");
-        LCHK(launch_filter(fa, o->k, grid_for(n), c->stream));
-    }
-    // 3. lookup + anchor count (index.rs:143-154, seeds.rs:42-57); the anchor
-    //    workspace keeps its capacity across batches, checked on the device
-    uint32_t *mz_n, *mz_poff, *a_cnt; uint64_t* a_off;
-    ENSURE(c->mz_n, uint32_t, mcap, mz_n); ENSURE(c->mz_poff, uint32_t, mcap, mz_poff);
-    ENSURE(c->a_cnt, uint32_t, n + 1, a_cnt); ENSURE(c->a_off, uint64_t, n + 1, a_off);
-    uint32_t* a_part;
-    ENSURE(c->a_part, uint32_t, (size_t)n * (SEED_PARTS - 1), a_part);
-    SeedArgs sa{n, c->d_rd_off, mz_base, mz_cnt, (const uint64_t*)c->sk1.x.p, (const uint32_t*)c->sk1.y.p, keep,
-                (const IxEntry*)c->dix->tab.p, c->log2cap, c->mid_occ, (const uint64_t*)c->dix->ix_pos.p, mz_n, mz_poff, a_cnt, a_off, nullptr, kl, o->k,
-                0, c->dix->ix_pos.cap / 8, mcap, out, a_part};
-    sa.abort = st32;
-    {
-        ProfScope ps(c, "seed_count");
-        LCHK(launch_seed_count(sa, grid_for(n), c->stream));
-    }
-    if (!c->ws_exact) c->cap_A = std::max<uint64_t>(c->cap_A, 3 * c->total_bases + 65536);   // exact-size mode: see reserve_anchor_ws
-    if (c->knob[MM2G_KNOB_WS_MIN] > 0 && !c->redo) c->cap_A = (uint64_t)c->knob[MM2G_KNOB_WS_MIN];   // tests: force the re-map
-    uint64_t A_cap = c->cap_A;
-    // reads heaviest first (anchor counts from seed_count): the hand-out order of
-    // seed_write, the sort and the chain work items; made by the anchor scan's block
-    uint32_t* rorder;
-    ENSURE(c->order, uint32_t, n, rorder);
-    {
-        ProfScope ps(c, "scan");
-        LCHK(launch_excl_scan(a_cnt, n, a_off, 0, 0, o->k, A_cap, st32, BS_ANCHORS, 2, c->stream, rorder));
-    }
-    if (int e = reserve_anchor_ws(c, st, A_cap)) return e;
-    uint64_t* keys = (uint64_t*)c->keys.p;
-    uint64_t* ktmp = (uint64_t*)c->keys_tmp.p;
-    int32_t* fb = (int32_t*)c->fbuf.p;      // the sort's per-key tags live here before the DP needs it
-    sa.keys = keys; sa.cap_keys = c->keys.cap / 8;
-    sa.order = rorder;
-    // 4. anchor sort (seeds.rs:58).  The singleton filter needs every max_dist_x
-    //    of both DP passes within one 2^CELL_SHIFT cell (DESIGN.md "Anchor sort");
-    //    it is off in debug mode (full anchor/DP arrays for the parity tests).
-    const bool filt = !full && !stop_after_sort && K[MM2G_KNOB_FILTER] && std::max(mdx0, mdx1) <= (1 << CELL_SHIFT);
-    const uint32_t sort_small_max = (uint32_t)std::min<int64_t>(K[MM2G_KNOB_SORT_SMALL], 4096);
+    if (int e = run_sketch(c, o->w, o->k, c->sk1, (int32_t*)B.st32, B.out, B.st)) return e;   // clears out[] and st[] first
+    B.mcap = c->sk1.cap;
+    B.mz_base = (const uint64_t*)c->sk1.base.p; B.mz_cnt = (const uint32_t*)c->sk1.cnt.p;
+    B.mz_x = (const uint64_t*)c->sk1.x.p; B.mz_y = (const uint32_t*)c->sk1.y.p;
+    if (int e = enqueue_filter(c, o, B)) return e;
+    if (int e = enqueue_seed_count(c, o, B)) return e;
+    // The singleton filter needs every max_dist_x of both DP passes within one
+    // 2^CELL_SHIFT cell (DESIGN.md "Anchor sort"); it is off in debug mode (full
+    // anchor/DP arrays for the parity tests).
+    B.filt = !full && !stop_after_sort && K[MM2G_KNOB_FILTER] && std::max(mdx0, mdx1) <= (1 << CELL_SHIFT);
+    B.sort_small_max = (uint32_t)std::min<int64_t>(K[MM2G_KNOB_SORT_SMALL], 4096);
     // fused seeding: k_sort_read's first pass makes the keys of the reads it sorts when their
     // minimizers (16 B each) fit in its LDS above the two cell bitmaps
-    uint32_t fuse_mmax = 0;
-    if (filt && K[MM2G_KNOB_SEED_FUSE]) {
+    if (B.filt && K[MM2G_KNOB_SEED_FUSE]) {
         SortArgs t{};
         t.cells = c->dix->cells;
         t.lds_words = (uint32_t)(std::max<int64_t>(0, K[MM2G_KNOB_SORT_LDS_KB]) * 256);
         const uint32_t LW = sort_read_lds_words(t), nw = (t.cells + 31) / 32;
-        if (LW > 2 * nw + 64 + 2048) fuse_mmax = std::min<uint32_t>((LW - 2 * nw - 64 - 2048) / 4, 0xffffu);   // 4 words per minimizer + 4096 u16 owner starts
+        if (LW > 2 * nw + 64 + 2048) B.fuse_mmax = std::min<uint32_t>((LW - 2 * nw - 64 - 2048) / 4, 0xffffu);   // 4 words per minimizer + 4096 u16 owner starts
     }
-    const uint32_t fuse_big = (filt && K[MM2G_KNOB_SEED_FUSE_BIG]) ? 1u : 0u;   // k_sort_big seeds the reads over 65535 anchors
-    sa.fuse_mmax = fuse_mmax; sa.small_max = sort_small_max; sa.fuse_big = fuse_big;
-    c->filt_last = filt; c->small_last = sort_small_max;
-    {
-        ProfScope ps(c, "seed_write");
-        LCHK(launch_seed_write(sa, grid_for(n), c->stream));
-    }
-    uint32_t* cnt2; uint64_t* smax; uint32_t* rlist;
-    ENSURE(c->cnt2, uint32_t, n, cnt2);
-    ENSURE(c->rlist, uint32_t, n + 2, rlist);
-    ENSURE(c->smax, uint64_t, n, smax);
+    B.fuse_big = (B.filt && K[MM2G_KNOB_SEED_FUSE_BIG]) ? 1u : 0u;   // k_sort_big seeds the reads over 65535 anchors
+    c->filt_last = B.filt; c->small_last = B.sort_small_max;
+    if (int e = enqueue_sort(c, o, B)) return e;
     const int64_t stop_at = K[MM2G_KNOB_STOP_AT];   // measurement only: later stages skipped, results invalid
-    // pass-0 chain parameters (main.rs:201-214): the sort's LB pass uses them too
-    ChainKParams P{};
-    P.max_dist_x = mdx0; P.max_dist_y = std::max(o->max_gap, o->bw); P.bw = o->bw; P.max_iter = 5000; P.max_skip = 25;
-    P.span = o->k; P.rescue_size = 1000; P.rescue_ratio_f = 1.0f - 0.1f; P.pass = 0; P.lut_n = o->bw + 1;
-    P.multi = multi ? 1 : 0;
-    const float gap = 0.01f * 0.8f * (float)o->k;
-    const int npass = stop_at == 3 ? 1 : 2;
     const bool chain = !stop_after_sort && stop_at != 1 && stop_at != 2;
-    SortArgs so{n, a_off, keys, ktmp, kl.qb, kl.rb, kl.n_seq, c->keys.cap / 8, (const uint32_t*)c->dix->goff.p,
-                filt ? c->dix->cells : 0u, cnt2, smax, sort_small_max, nullptr, 0u,
-                (uint32_t)std::max<int64_t>(1, std::min<int64_t>(K[MM2G_KNOB_SEG_SMALL], SEG_THREAD)), nullptr};
-    so.abort = st32;
-    so.meta = (uint32_t*)fb;
-    so.rlist = rlist; so.rcount = rlist + n; so.rwork = rlist + n + 1;
-    so.order = rorder;
-    so.lds_words = (uint32_t)(std::max<int64_t>(0, K[MM2G_KNOB_SORT_LDS_KB]) * 256);
-    so.fuse_mmax = fuse_mmax;
-    so.fuse_big = fuse_big; so.a_part = a_part;
-    so.read_tiny = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(K[MM2G_KNOB_READ_TINY], 1024));
-    so.big_tiny = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(K[MM2G_KNOB_BIG_TINY], 2048));
-    so.small_reg = K[MM2G_KNOB_SMALL_REG] ? 1u : 0u;
-    so.big_wnd = (uint32_t)std::max<int64_t>(0, K[MM2G_KNOB_BIG_WND]);
-    so.rd_off = c->d_rd_off; so.mz_base = mz_base; so.mz_cnt = mz_cnt; so.mz_y = (const uint32_t*)c->sk1.y.p;
-    so.mz_n = mz_n; so.mz_poff = mz_poff; so.ix_pos = (const uint64_t*)c->dix->ix_pos.p; so.kl = kl; so.span = o->k;
-    so.cap_pos = c->dix->ix_pos.cap / 8;
-    uint64_t* sprof = nullptr;
-    if (K[MM2G_KNOB_SORT_PROF]) { HIPCHK(hipMalloc(&sprof, (size_t)n * 192)); HIPCHK(hipMemsetAsync(sprof, 0, (size_t)n * 192, c->stream)); so.prof = sprof; }
-    if (stop_at != 1) {
-    {
-        ProfScope ps(c, "sort_small");
-        LCHK(launch_sort_read(0, so, c->stream));
-    }
-    {
-        ProfScope ps(c, "sort_large");
-        LCHK(launch_sort_read(1, so, c->stream));
-    }
-    {
-        ProfScope ps(c, so.cells ? "sort_big" : "sort_radix");   // reads k_sort_read listed: buckets (filter on) or radix
-        LCHK(launch_sort_read(2, so, c->stream));
-    }
-    if (sprof) dump_sort_prof(c, sprof, n);
-    // the sorted anchors are in the tmp buffer: swap the roles for everything downstream
-    std::swap(c->keys.p, c->keys_tmp.p); std::swap(c->keys.cap, c->keys_tmp.cap);
-    std::swap(keys, ktmp);
-    }
     if (chain) {
-        // 5. chain DP + fallback + rescue
-        if (int e = run_chain(c, n, c->d_rd_off, P, gap, npass, mdx1, std::max(o->max_gap, o->bw_long), o->bw_long, A_cap,
-                              a_off, a_cnt, keys, ktmp, cnt2, smax, out, st32, full, st, true, mz_cnt))
-            return e;
-        // 6. dv inputs (paf.rs:156-199): sketch with the INDEX w/k (Q3)
-        const bool sep = (H.w != o->w || H.k != o->k);
-        c->dv_separate = sep;
-        if (sep) {
-            if (!(H.w > 0 && H.w < 256 && H.k > 0 && H.k <= 28)) return set_err(MM2G_E_ARG, "index w/k invalid for the dv sketch");
-            if (int e = run_sketch(c, H.w, H.k, c->sk2, (int32_t*)(st32 + 1))) return e;
-        }
-        SketchBufs& D = sep ? c->sk2 : c->sk1;
-        DvArgs da{n, a_off, keys, (const uint32_t*)ktmp, (const uint64_t*)D.base.p, (const uint32_t*)D.cnt.p, (const uint32_t*)D.y.p, kl, o->k,
-                  out, c->keys.cap / 8, D.y.cap / 4};
-        da.abort = st32;
-        da.strict = (H.k & 1) && c->knob[MM2G_KNOB_DV_PAR] ? 1u : 0u;   // odd k: positions strictly increase
-        // reads whose dv sketch outgrows k_dv's 4096 staged positions (~2 per w+1 bases): a workgroup each
-        da.long_m = da.strict && 2ull * c->max_read_len / (uint64_t)(H.w + 1) + 64 > 4096 ? 0xffffffffu : 0u;
-        ProfScope ps(c, "dv");
-        if (stop_at != 4) LCHK(launch_dv(da, c->stream));
+        // 5. chain DP + fallback + rescue; pass-0 chain parameters: main.rs:201-214
+        ChainJob J;
+        J.n = n; J.rd_off = c->d_rd_off; J.a_off = B.a_off; J.a_cnt = B.a_cnt;
+        J.keys = B.keys; J.ktmp = B.ktmp; J.cnt2 = B.cnt2; J.smax = B.smax;
+        J.out = B.out; J.abort = B.st32; J.stat = B.st;
+        J.P0.max_dist_x = mdx0; J.P0.max_dist_y = std::max(o->max_gap, o->bw); J.P0.bw = o->bw; J.P0.max_iter = 5000; J.P0.max_skip = 25;
+        J.P0.span = o->k; J.P0.rescue_size = 1000; J.P0.rescue_ratio_f = 1.0f - 0.1f; J.P0.pass = 0; J.P0.lut_n = o->bw + 1;
+        J.P0.multi = multi ? 1 : 0;
+        J.gap = 0.01f * 0.8f * (float)o->k;
+        J.npass = stop_at == 3 ? 1 : 2;
+        J.mdx1 = mdx1; J.mdy1 = std::max(o->max_gap, o->bw_long); J.bw_long = o->bw_long;
+        J.A_cap = B.A_cap; J.full = full; J.order_ready = true; J.sum_mz = B.mz_cnt;
+        if (int e = run_chain(c, J)) return e;
+        if (int e = enqueue_dv(c, o, B)) return e;
     }
-    if (!chain) LCHK(launch_batch_sums(n, mz_cnt, cnt2, st, c->stream));   // (else the last chain pass's k_seg_items)
-    HIPCHK(hipMemcpyAsync(c->h_out, out, (size_t)n * sizeof(ReadOut), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_stat, st, STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    if (!chain) LCHK(launch_batch_sums(n, B.mz_cnt, B.cnt2, B.st, c->stream));   // (else the last chain pass's k_seg_items)
+    HIPCHK(hipMemcpyAsync(c->h_out, B.out, (size_t)n * sizeof(ReadOut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_stat, B.st, STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipEventRecord(c->ev_done, c->stream));
     c->mapped = true;
     return 0;
@@ -1373,21 +1402,21 @@ static int wait_batch(mm2g_ctx* c) {
     for (int it = 0;; ++it) {
         HIPCHK(hipEventSynchronize(c->ev_done));
         const uint32_t* s32 = (const uint32_t*)c->h_stat;
-        const uint32_t bits = s32[0], dv_ovf = s32[1];
+        const uint32_t bits = s32[2 * ST_FLAGS], dv_ovf = s32[ST32_DV_OVF];
         if (!bits && !dv_ovf) break;
         if (it >= 4) return set_err(MM2G_E_STATE, "batch workspaces did not converge (status %u)", bits);
         if (bits & BS_SKETCH) { if (int e = sketch_exact_layout(c, c->sk1)) return e; }
         if (dv_ovf) { if (int e = sketch_exact_layout(c, c->sk2)) return e; }
         if ((bits & BS_SKETCH) || dv_ovf) c->views_off = true;   // a view may have overflowed its own slot
-        if (bits & BS_TAB) c->cap_tab = std::max(c->cap_tab, c->h_stat[1] + c->h_stat[1] / 4 + 1024);
-        if (bits & BS_ANCHORS) c->cap_A = std::max(c->cap_A, c->h_stat[2] + c->h_stat[2] / 4 + 65536);
+        if (bits & BS_TAB) c->cap_tab = std::max(c->cap_tab, c->h_stat[ST_TAB] + c->h_stat[ST_TAB] / 4 + 1024);
+        if (bits & BS_ANCHORS) c->cap_A = std::max(c->cap_A, c->h_stat[ST_ANCHORS] + c->h_stat[ST_ANCHORS] / 4 + 65536);
         const mm2g_map_opts o = c->last_opts;
         c->redo = true;
         const int e = map_enqueue(c, &o, c->stop_after_sort);
         c->redo = false;
         if (e) return e;
     }
-    c->n_anchors = c->h_stat[2];
+    c->n_anchors = c->h_stat[ST_ANCHORS];
     c->prof_collect();
     c->collected = true;
     c->views_off = false;
@@ -1516,14 +1545,15 @@ int mm2g_batch_results(mm2g_ctx* c, mm2g_read_result* res, uint32_t n) {
     if (int e = wait_batch(c)) return e;
     const HostIndex& H = *c->hidx;
     const int kdv = c->dv_separate ? H.k : c->last_opts.k;
-    uint64_t cnt[6] = {c->total_bases, c->h_stat[3], 0, c->n_anchors, 0, 0};
-    uint64_t scls[3] = {0, 0, 0};   // anchors per sort class (counters 18-20, launch_sort_read)
+    const uint64_t* hs = c->h_stat;
+    uint64_t cn[CN_COUNT] = {};
+    cn[CN_BASES] = c->total_bases; cn[CN_MINIMIZERS] = hs[ST_MINIMIZERS]; cn[CN_ANCHORS] = c->n_anchors;
     c->h_res.resize(c->n_reads);
     for (uint32_t i = 0; i < c->n_reads; ++i) {
         const ReadOut& o = c->h_out[i];
-        cnt[4] += (o.flags & RF_RESCUED) ? (uint64_t)o.n_anchors : 0;
-        cnt[5] += o.dp_pairs;
-        cnt[2] += (uint64_t)o.m_kept;
+        cn[CN_RESCUED_ANCHORS] += (o.flags & RF_RESCUED) ? (uint64_t)o.n_anchors : 0;
+        cn[CN_DP_PAIRS] += o.dp_pairs;
+        cn[CN_KEPT_MINIMIZERS] += (uint64_t)o.m_kept;
         mm2g_read_result& r = c->h_res[i];
         memset(&r, 0, sizeof r);
         const uint64_t L = c->h_rd_off[i + 1] - c->h_rd_off[i];
@@ -1532,16 +1562,13 @@ int mm2g_batch_results(mm2g_ctx* c, mm2g_read_result* res, uint32_t n) {
         r.n_anchors = o.n_anchors;
         {
             const uint32_t na = (uint32_t)o.n_anchors;
-            if (na > 1) scls[na <= c->small_last ? 0 : (c->filt_last && na <= 65535u) ? 1 : 2] += na;
+            if (na > 1) cn[na <= c->small_last ? CN_SORT_SMALL_ANCHORS : (c->filt_last && na <= 65535u) ? CN_SORT_CELL_ANCHORS : CN_SORT_WHOLE_ANCHORS] += na;
         }
         if (!(o.flags & RF_MAPPED)) continue;
         r.flags = MM2G_R_MAPPED | ((o.flags & RF_RESCUED) ? MM2G_R_RESCUED : 0) | ((o.flags & RF_DV_FOUND) ? MM2G_R_DV_FOUND : 0) |
                   ((o.flags & RF_PANIC) ? MM2G_R_PANIC : 0);
         r.score = o.score; r.cm = o.cm; r.qs = o.qs; r.qe = o.qe; r.ts = o.ts; r.te = o.te;
-        const uint32_t g = (uint32_t)o.group;
-        if (g == 2u * H.n_seq) { r.rid = 0x7fffffff; r.rev = 1; }
-        else if (g >= H.n_seq) { r.rid = (int32_t)(g - H.n_seq); r.rev = 1; }
-        else { r.rid = (int32_t)g; r.rev = 0; }
+        group_to_rid_rev((uint32_t)o.group, H.n_seq, r.rid, r.rev);
         r.n_match = o.n_match; r.dv_st = o.dv_st; r.dv_en = o.dv_en; r.m_dv = o.m_dv;
         r.sum_k = (int64_t)o.m_dv * kdv;      // query spans are all k (non-HPC)
         // dv (paf.rs:189-199): f32 op by op, glibc powf
@@ -1562,17 +1589,16 @@ int mm2g_batch_results(mm2g_ctx* c, mm2g_read_result* res, uint32_t n) {
     if (c->multi_last) { if (int e = multi_epilogue(c)) return e; }
     else c->multi.clear();
     if (res && n) memcpy(res, c->h_res.data(), (size_t)n * sizeof(mm2g_read_result));
-    for (int t = 0; t < 6; ++t) c->counters[t] = cnt[t];
-    c->counters[6] = c->h_stat[4];    // anchors left after the sort's singleton filter (the DP input)
-    for (int t = 0; t < 6; ++t) c->counters[7 + t] = c->h_stat[8 + t];   // anchors per chain kernel class and pass
-    c->counters[13] = c->h_stat[5];   // DP anchors whose keys k_chain_seg streams (pass 0; the rest: sparse items)
-    c->counters[14] = c->lb_ran0 ? c->h_stat[4] : 0;   // ... that k_chain_lb streams (pass 0; 0 when it did not run)
-    c->counters[15] = c->h_stat[6];   // rescued anchors whose keys k_chain_seg streams (pass 1)
-    c->counters[16] = c->h_stat[7];   // anchors of the reads k_sort_read seeds itself (fused seeding)
-    c->counters[17] = c->h_stat[14];  // ... and their minimizers
-    for (int t = 0; t < 3; ++t) c->counters[18 + t] = scls[t];
-    c->counters[21] = c->h_stat[15];  // anchors of the reads k_sort_big seeds itself
-    c->counters[22] = c->h_stat[16];  // ... and their minimizers
+    cn[CN_DP_ANCHORS] = hs[ST_DP_ANCHORS];
+    for (int t = 0; t < ST_CLASSES * ST_PASSES; ++t) cn[CN_LONG_ANCHORS + t] = hs[ST_SEG_CLASS + t];   // per chain kernel class and pass
+    cn[CN_SEG_STREAM_ANCHORS] = hs[ST_SEG_STREAMED];
+    cn[CN_LB_STREAM_ANCHORS] = c->lb_ran0 ? hs[ST_DP_ANCHORS] : 0;
+    cn[CN_SEG_STREAM_RESCUE] = hs[ST_SEG_STREAMED + 1];
+    cn[CN_FUSED_ANCHORS] = hs[ST_FUSED_ANCHORS];
+    cn[CN_FUSED_MINIMIZERS] = hs[ST_FUSED_MZ];
+    cn[CN_FUSED_BIG_ANCHORS] = hs[ST_BIG_ANCHORS];
+    cn[CN_FUSED_BIG_MINIMIZERS] = hs[ST_BIG_MZ];
+    memcpy(c->counters, cn, sizeof cn);
     return 0;
 }
 
@@ -1689,7 +1715,7 @@ int mm2g_batch_sketch(mm2g_ctx* c, int w, int k, uint32_t rid, uint64_t* out_off
     int32_t* ovf;
     unsigned long long* st;
     ENSURE(c->dstat, unsigned long long, STAT_WORDS, st);
-    ovf = (int32_t*)st + 1;
+    ovf = (int32_t*)st + ST32_DV_OVF;
     for (int it = 0;; ++it) {
         HIPCHK(hipMemsetAsync(st, 0, STAT_WORDS * 8, c->stream));
         if (int e = run_sketch(c, w, k, B, ovf)) return e;
@@ -1806,11 +1832,7 @@ int mm2g_chain_batch(mm2g_ctx* c, const mm2g_chain_params* p, uint32_t n, const 
         return set_err(MM2G_E_UNSUP, "min_cnt %d with min_chain_score %d <= span %lld: Rust sort_unstable tie order (DESIGN.md \"-n <= 1\")",
                        p->min_cnt, p->min_chain_score, (long long)span);
     KeyLayout kl;
-    kl.n_seq = (uint32_t)max_rid + 1;
-    kl.qb = std::max<uint32_t>(1, bit_width(max_q));
-    kl.rb = std::max<uint32_t>(1, bit_width(max_p));
-    kl.gb = std::max<uint32_t>(1, bit_width(2ull * kl.n_seq));
-    if (kl.qb + kl.rb + kl.gb > 64) return set_err(MM2G_E_UNSUP, "anchor key needs %u bits (> 64)", kl.qb + kl.rb + kl.gb);
+    if (int e = make_key_layout(max_q, max_p, (uint32_t)max_rid + 1, kl)) return e;
     std::vector<uint64_t> keys(A), ho(n + 1), hro(n + 1, 0);
     std::vector<uint32_t> hcnt(n);
     for (uint32_t r = 0; r < n; ++r) {
@@ -1848,14 +1870,16 @@ int mm2g_chain_batch(mm2g_ctx* c, const mm2g_chain_params* p, uint32_t n, const 
     }
     HIPCHK(hipMemsetAsync(smax, 0, ((size_t)n + 1) * 8, c->stream));
     HIPCHK(hipMemsetAsync(out, 0, sizeof(ReadOut) * ((size_t)n + 1), c->stream));
-    ChainKParams P{};
+    ChainJob J;
+    J.n = n; J.rd_off = dro; J.a_off = doff; J.a_cnt = dcnt; J.keys = dk; J.ktmp = dt; J.cnt2 = cnt2; J.smax = smax; J.out = out;
+    ChainKParams& P = J.P0;
     P.max_dist_x = std::max(p->max_dist_x, p->bw); P.max_dist_y = std::max(p->max_dist_y, p->bw);   // lchain.rs:63-66
     P.bw = p->bw; P.max_iter = p->max_chain_iter; P.max_skip = p->max_chain_skip;
     P.span = (int32_t)span; P.rescue_size = p->rmq_rescue_size; P.rescue_ratio_f = 1.0f - p->rmq_rescue_ratio; P.pass = 0; P.lut_n = p->bw + 1;
-    const int32_t mdx1 = std::max(p->max_dist_x, p->bw_long), mdy1 = std::max(p->max_dist_y, p->bw_long);
-    if (int e = run_chain(c, n, dro, P, p->chn_pen_gap, rescue ? 2 : 1, mdx1, mdy1, p->bw_long, A_cap, doff, dcnt, dk, dt, cnt2, smax, out,
-                          nullptr, c->debug || f || pprev))
-        return e;
+    J.gap = p->chn_pen_gap; J.npass = rescue ? 2 : 1;
+    J.mdx1 = std::max(p->max_dist_x, p->bw_long); J.mdy1 = std::max(p->max_dist_y, p->bw_long); J.bw_long = p->bw_long;
+    J.A_cap = A_cap; J.full = c->debug || f || pprev;
+    if (int e = run_chain(c, J)) return e;
     std::vector<ReadOut> ho2(n);
     if (n) HIPCHK(hipMemcpyAsync(ho2.data(), out, (size_t)n * sizeof(ReadOut), hipMemcpyDeviceToHost, c->stream));
     if (f && A) HIPCHK(hipMemcpyAsync(f, c->fbuf.p, A * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1872,10 +1896,7 @@ int mm2g_chain_batch(mm2g_ctx* c, const mm2g_chain_params* p, uint32_t n, const 
         if (!(o.flags & RF_MAPPED)) continue;
         R.flags = MM2G_R_MAPPED | ((rescue && (o.flags & RF_RESCUED)) ? MM2G_R_RESCUED : 0) | ((o.flags & RF_PANIC) ? MM2G_R_PANIC : 0);
         R.score = o.score; R.cm = o.cm; R.qs = o.qs; R.qe = o.qe; R.ts = o.ts; R.te = o.te;
-        const uint32_t g = (uint32_t)o.group;
-        if (g == 2u * kl.n_seq) { R.rid = 0x7fffffff; R.rev = 1; }
-        else if (g >= kl.n_seq) { R.rid = (int32_t)(g - kl.n_seq); R.rev = 1; }
-        else { R.rid = (int32_t)g; R.rev = 0; }
+        group_to_rid_rev((uint32_t)o.group, kl.n_seq, R.rid, R.rev);
         // chain_dp_all's chains[0]: the pprev walk from best_i, reversed to ascending (lchain.rs:162-173)
         if (chain)
             for (int32_t t = 0; t < o.cm; ++t) chain[ho[r] + t] = cb[ho[r] + (uint64_t)(o.cm - 1 - t)];
@@ -1985,3 +2006,122 @@ int mm2g_batch_counters(mm2g_ctx* c, uint64_t* out, int n) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ profiling dumps
+// MM2G_KNOB_SORT_PROF: phase times of k_sort_read (wall clock, 100 MHz) to stderr
+static void dump_sort_prof(mm2g_ctx* c, uint64_t* d, uint32_t n) {
+    std::vector<uint64_t> h((size_t)n * 24);
+    if (hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) return;
+    (void)hipFree(d);
+    double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot = 0, a0 = 0, a2 = 0, np = 0, nleg = 0, nbigp = 0, ktiny = 0, klong = 0, ksrch = 0;
+    uint64_t t_lo = ~0ULL, t_hi = 0;
+    uint32_t m = 0;
+    std::vector<uint32_t> q0, q2, q3;
+    for (uint32_t r = 0; r < n; ++r) {
+        const uint64_t* p = &h[(size_t)r * 24];
+        if (!p[11]) continue;
+        q3.push_back((uint32_t)p[13]);
+        ++m;
+        for (int k = 0; k < 8; ++k) ph[k] += (double)p[k];
+        tot += (double)(p[11] - p[10]);
+        a0 += (double)p[8]; a2 += (double)(uint32_t)p[9];
+        if ((p[9] >> 32) == 0xffffu) nleg += 1;
+        else if ((p[9] >> 32) == 0xfffeu) nbigp += 1;
+        else np += (double)(p[9] >> 32);
+        t_lo = std::min(t_lo, p[10]); t_hi = std::max(t_hi, p[11]);
+        q0.push_back((uint32_t)p[8]); q2.push_back((uint32_t)p[9]);
+        ktiny += (double)(uint32_t)p[14]; klong += (double)(p[14] >> 32); ksrch += (double)p[15];
+    }
+    if (!m) return;
+    std::sort(q0.begin(), q0.end()); std::sort(q2.begin(), q2.end()); std::sort(q3.begin(), q3.end());
+    auto Q = [](const std::vector<uint32_t>& v, double f) { return v[std::min(v.size() - 1, (size_t)(f * v.size()))]; };
+    fprintf(stderr, "[sort_prof] A0 q10/50/90/99/max=%u/%u/%u/%u/%u  A q10/50/90/99/max=%u/%u/%u/%u/%u  kept cells q10/50/90/99/max=%u/%u/%u/%u/%u\n",
+            Q(q0, .1), Q(q0, .5), Q(q0, .9), Q(q0, .99), q0.back(), Q(q2, .1), Q(q2, .5), Q(q2, .9), Q(q2, .99), q2.back(),
+            Q(q3, .1), Q(q3, .5), Q(q3, .9), Q(q3, .99), q3.back());
+    fprintf(stderr, "[sort_prof] reads=%u (whole-read radix %.0f, bucket path %.0f) A0=%.0f A=%.0f nbig=%.2f windows=%.2f us/read: p1+kc=%.1f p2=%.1f gather=%.1f fuse_stage=%.1f chunk=%.1f rank=%.1f p4b/radix=%.1f total=%.1f span_us=%.1f concurrency=%.1f\n",
+            m, nleg, nbigp, a0 / m, a2 / m, np / m, ph[7] / m, ph[0] / m / 100, ph[1] / m / 100, ph[2] / m / 100, ph[3] / m / 100, ph[4] / m / 100,
+            ph[5] / m / 100, ph[6] / m / 100, tot / m / 100, (double)(t_hi - t_lo) / 100, tot / (double)(t_hi - t_lo));
+    fprintf(stderr, "[sort_prof] keys per read in segments <= %u: %.0f, 17..64: %.0f, > 64: %.0f (%.2f other-chunk searches each)\n",
+            16u, ktiny / m, (a2 - ktiny - klong) / m, klong / m, klong > 0 ? ksrch / klong : 0.0);
+}
+
+// MM2G_SKETCH_PROF: phase times of k_sketch summed over each read's tiles
+static void dump_sketch_prof(mm2g_ctx* c, uint64_t* d, uint32_t n) {
+    std::vector<uint64_t> h((size_t)n * 8);
+    if (hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) return;
+    (void)hipFree(d);
+    double ph[5] = {0, 0, 0, 0, 0}, L = 0;
+    uint32_t m = 0;
+    uint64_t t_hi = 0, tiles = 0, slow = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+        const uint64_t* p = &h[(size_t)r * 8];
+        if (!p[5]) continue;
+        ++m;
+        tiles += p[7] >> 32; slow += p[7] & 0xffffffffULL;
+        for (int k = 0; k < 5; ++k) ph[k] += (double)p[k];
+        L += (double)p[5];
+        t_hi = std::max(t_hi, p[6]);
+    }
+    if (!m) return;
+    double tot = ph[0] + ph[1] + ph[2] + ph[3] + ph[4];
+    fprintf(stderr, "[sketch_prof] reads=%u len=%.0f us/read: stage=%.1f warmup=%.1f phase1=%.1f phase2=%.1f tail=%.1f total=%.1f; exact-path tiles %.1f%%\n",
+            m, L / m, ph[0] / m / 100, ph[1] / m / 100, ph[2] / m / 100, ph[3] / m / 100, ph[4] / m / 100, tot / m / 100,
+            tiles ? 100.0 * (double)slow / (double)tiles : 0.0);
+}
+
+// MM2G_KNOB_LSEG_PROF, before a pass's DP kernels: per-segment times (ca.lseg_prof) and the phase counters (ca.gprof)
+static int chain_prof_begin(mm2g_ctx* c, ChainArgs& ca) {
+    ca.lseg_prof = c->knob[MM2G_KNOB_LSEG_PROF] ? 1u : 0u;
+    unsigned long long* gprof = nullptr;
+    if (ca.lseg_prof) {
+        HIPCHK(hipMalloc(&gprof, 32 * 8));
+        HIPCHK(hipMemsetAsync(gprof, 0, 32 * 8, c->stream));
+    }
+    ca.gprof = gprof;
+    return 0;
+}
+
+// ... and after them: k_chain_giant phase sums (wall clock, 100 MHz), k_chain_long per-anchor cycles,
+// the slowest long segments of the pass
+static int dump_chain_prof(mm2g_ctx* c, int pass, ChainArgs& ca) {
+    unsigned long long g[32];
+    HIPCHK(hipMemcpyAsync(g, ca.gprof, sizeof g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)hipFree(ca.gprof);
+    ca.gprof = nullptr;
+    fprintf(stderr, "[giant_prof] pass %d: %llu segments, %llu anchors, %llu iterations, %llu pins, %llu fallbacks; block-us: total %.0f "
+                    "setup %.0f eval %.0f changed %.0f improve %.0f children %.0f markcheck %.0f pin %.0f write %.0f\n",
+            pass, g[8], g[9], g[10], g[11], g[13], g[12] / 100.0, g[0] / 100.0, g[1] / 100.0, g[2] / 100.0, g[3] / 100.0,
+            g[4] / 100.0, g[5] / 100.0, g[6] / 100.0, g[7] / 100.0);
+    const double np_ = (double)std::max<unsigned long long>(g[17] + g[19], 1);
+    fprintf(stderr, "[long_prof] pass %d: %llu anchors in long segments, %llu committed by the speculative block pass in %llu rounds; "
+                    "per-anchor path: %llu settled by the simple/shortcut step, %llu exact (%llu 64-lane window steps in all); "
+                    "shader cycles per per-anchor-path anchor: st %.0f simple %.0f exact %.0f tail %.0f\n",
+            pass, g[16], g[24], g[25], g[17], g[19], g[18], g[20] / np_, g[21] / np_, g[22] / np_, g[23] / np_);
+    fprintf(stderr, "[long_prof] pass %d heaviest segment: %llu anchors committed speculatively in %llu rounds, %llu by the per-anchor path; "
+                    "shader cycles: speculative %llu, per-anchor path %llu, segment %llu\n",
+            pass, g[26], g[27], g[28], g[30], g[29], g[31]);
+    uint32_t nl = 0;
+    HIPCHK(hipMemcpyAsync(&nl, ca.lseg_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    nl = std::min(nl, ca.lseg_cap);
+    std::vector<uint4> ls(nl);
+    if (nl) HIPCHK(hipMemcpy(ls.data(), ca.lseg, (size_t)nl * 16, hipMemcpyDeviceToHost));
+    // lseg[].w: wall-clock ticks (100 MHz) of the kernel that ran the segment; bit 31 = k_chain_giant's
+    const uint32_t GBIT = 0x80000000u;
+    std::sort(ls.begin(), ls.end(), [&](const uint4& x, const uint4& y) { return (x.w & ~GBIT) > (y.w & ~GBIT); });
+    double tot = 0, tot_g = 0; uint32_t ng = 0;
+    for (auto& v : ls) { tot += v.w & ~GBIT; if (v.w & GBIT) { tot_g += v.w & ~GBIT; ++ng; } }
+    fprintf(stderr, "[lseg_prof] pass %d: %u long segments (%u by k_chain_giant), sum %.0f us (giant %.0f us); slowest:", pass, nl, ng,
+            tot / 100, tot_g / 100);
+    for (size_t i = 0; i < ls.size() && i < 8; ++i) {
+        ReadOut ro;
+        HIPCHK(hipMemcpy(&ro, ca.out + ls[i].x, sizeof ro, hipMemcpyDeviceToHost));
+        fprintf(stderr, " (read %u len %u %s %.0f us, read j-steps %u pairs %llu)", ls[i].x, ls[i].z - ls[i].y,
+                (ls[i].w & GBIT) ? "giant" : "long", (ls[i].w & ~GBIT) / 100.0, ro.n_steps, (unsigned long long)ro.dp_pairs);
+    }
+    fprintf(stderr, "\n");
+    return 0;
+}

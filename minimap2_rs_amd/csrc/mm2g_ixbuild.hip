@@ -544,7 +544,9 @@ bool build_index_gpu(int device, const std::vector<const uint8_t*>& seqs, const 
         hipLaunchKernelGGL(k_hpc_span, dim3(nb), dim3(256), 0, st, d_seq, total, d_coff, (uint32_t)n, k, d_skip, d_span);
         IXCHK(hipGetLastError());
     }
-    SketchArgs sa{d_seq, nullptr, nv, w, k, d_vbase, d_vend, d_mx, d_my, d_cnt, d_ovf};
+    SketchArgs sa{};
+    sa.seq = d_seq; sa.n = nv; sa.w = w; sa.k = k;
+    sa.out_base = d_vbase; sa.out_end = d_vend; sa.mz_x = d_mx; sa.mz_y = d_my; sa.mz_cnt = d_cnt; sa.overflow = d_ovf;
     sa.view_off = d_voff; sa.view_len = d_vlen; sa.view_pre = d_vpre; sa.emit_from = d_vfrom; sa.view_last = d_vlast;
     sa.hpc_span = d_span;
     if (nt4) {   // contig r = "read" r of an nt4 batch; view r reads contig v_rid[r]

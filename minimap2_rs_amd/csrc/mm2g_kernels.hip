@@ -1589,9 +1589,9 @@ __global__ __launch_bounds__(NT) void k_sort_read(SortArgs a) {
             uint32_t* My = Mp + fm;                // query y
             uint32_t* Mh = My + fm;                // raw n (IX_INLINE | position high word for a Single)
             const uint64_t mb = a.mz_base[r];
-            if (tid == 0 && a.abort) {             // status words 7 / 14: anchors and minimizers seeded here (bench pricing)
-                atomicAdd((unsigned long long*)a.abort + 7, (unsigned long long)A0);
-                atomicAdd((unsigned long long*)a.abort + 14, (unsigned long long)fm);
+            if (tid == 0 && a.abort) {             // anchors and minimizers seeded here (bench pricing)
+                atomicAdd(stat_word(a.abort, ST_FUSED_ANCHORS), (unsigned long long)A0);
+                atomicAdd(stat_word(a.abort, ST_FUSED_MZ), (unsigned long long)fm);
             }
             uint32_t carry = 0;
             constexpr int FS = 2;   // minimizers per thread per step (a 10 kb read's ~1.8 k in one step)
@@ -2137,9 +2137,9 @@ __global__ __launch_bounds__(1024) void k_sort_big(SortArgs a) {
             const uint32_t cend = ce * 64 < m ? ce * 64 : m;
             const int32_t qlen = (int32_t)(a.rd_off[r + 1] - a.rd_off[r]);
             uint32_t run = wv ? a.a_part[(uint64_t)r * (SEED_PARTS - 1) + (uint32_t)wv - 1] : 0u;
-            if (tid == 0 && a.abort) {             // status words 15 / 16: anchors and minimizers seeded here (bench pricing)
-                atomicAdd((unsigned long long*)a.abort + 15, (unsigned long long)A0);
-                atomicAdd((unsigned long long*)a.abort + 16, (unsigned long long)m);
+            if (tid == 0 && a.abort) {             // anchors and minimizers seeded here (bench pricing)
+                atomicAdd(stat_word(a.abort, ST_BIG_ANCHORS), (unsigned long long)A0);
+                atomicAdd(stat_word(a.abort, ST_BIG_MZ), (unsigned long long)m);
             }
             constexpr int U = 8;
             for (uint32_t c0 = cb * 64; c0 < cend; c0 += 64) {
@@ -2671,7 +2671,7 @@ __global__ __launch_bounds__(1024) void k_seg_items(ChainArgs a) {
         if (tid < 2) {
             unsigned long long x = 0;
             for (int t = 0; t < 16; ++t) x += ws[tid][t];
-            a.bsum[3 + tid] = x;
+            a.bsum[ST_MINIMIZERS + tid] = x;   // and ST_DP_ANCHORS
         }
     }
 }
@@ -3337,6 +3337,7 @@ __global__ __launch_bounds__(256) void k_chain_med(ChainArgs a) {
 // long segments by descending length (largest-first hand-out to k_chain_long);
 // also the anchors each chain kernel gets (roofline accounting, mm2g_batch_counters):
 // seg_stat[0] long segments below giant_min, [1] from giant_min on, [2] medium segments
+// (the pass's ST_CLASSES words from ST_SEG_CLASS on)
 __global__ __launch_bounds__(1024) void k_lseg_order(ChainArgs a) {
     __shared__ uint32_t hist[33], offs[33];
     __shared__ unsigned long long ssum[3][16];
@@ -4647,9 +4648,8 @@ __global__ __launch_bounds__(1024) void k_excl_scan(const uint32_t* in, uint32_t
     if (order) read_order_block(n, in, order, hist, s_sc);   // the anchor scan also orders the reads (one launch less)
 }
 
-// per-batch sums for mm2g_batch_counters (st[3] = minimizers, st[4] = anchors in the DP)
+// per-batch sums for mm2g_batch_counters (st[ST_MINIMIZERS], st[ST_DP_ANCHORS] = anchors in the DP)
 __global__ __launch_bounds__(1024) void k_batch_sums(uint32_t n, const uint32_t* mz_cnt, const uint32_t* cnt2, unsigned long long* st) {
-    // st[3] minimizers, st[4] anchors in the DP
     __shared__ unsigned long long ws[2][16];
     unsigned long long v[2] = {0, 0};
     for (uint32_t i = threadIdx.x; i < n; i += 1024) { v[0] += mz_cnt[i]; v[1] += cnt2 ? cnt2[i] : 0u; }
@@ -4659,7 +4659,7 @@ __global__ __launch_bounds__(1024) void k_batch_sums(uint32_t n, const uint32_t*
     if (threadIdx.x < 2) {
         unsigned long long x = 0;
         for (int t = 0; t < 16; ++t) x += ws[threadIdx.x][t];
-        st[3 + threadIdx.x] = x;
+        st[ST_MINIMIZERS + threadIdx.x] = x;
     }
 }
 
@@ -4858,6 +4858,12 @@ int launch_sketch(const SketchArgs& a, int n_blocks, hipStream_t st) {
     LAUNCH_CHECK();
     return 0;
 }
+// compute units of the current device (`fallback` when the runtime cannot tell)
+static int cu_count(int fallback) {
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return fallback;
+    return ncu;
+}
 int launch_filter(const FilterArgs& a, int k, int n_blocks, hipStream_t st) {
     if (a.n == 0) return 0;
     hipLaunchKernelGGL(k_filter_lds, dim3(a.n), dim3(256), 0, st, a, k);
@@ -4865,8 +4871,7 @@ int launch_filter(const FilterArgs& a, int k, int n_blocks, hipStream_t st) {
     (void)n_blocks;
     // persistent: one workgroup per CU (its LDS), reads taken by grid stride; most reads of
     // 10 kb batches are k_filter_lds's and are skipped after one load of their count
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int ncu = cu_count(256);
     hipLaunchKernelGGL(k_filter, dim3(std::min<uint32_t>(a.n, (uint32_t)std::max(ncu, 1))), dim3(1024), FB_LDS, st, a, k);
     LAUNCH_CHECK();
     return 0;
@@ -4892,10 +4897,10 @@ uint32_t sort_read_lds_words(const SortArgs& a) {
     size_t lds = std::max<size_t>(a.lds_words ? (size_t)a.lds_words * 4 : (size_t)SORT_LDS, bmb);
     return (uint32_t)(std::min<size_t>(lds, (size_t)SORT_LDS) / 4);
 }
-int launch_sort_read(int stage, const SortArgs& a, hipStream_t st) {
+int launch_sort_read(SortStage stage, const SortArgs& a, hipStream_t st) {
     if (a.n == 0) return 0;
-    if (stage == 0) hipLaunchKernelGGL(k_sort_small, dim3(a.n), dim3(256), 0, st, a);
-    else if (stage == 1) {
+    if (stage == SortStage::Small) hipLaunchKernelGGL(k_sort_small, dim3(a.n), dim3(256), 0, st, a);
+    else if (stage == SortStage::Read) {
         const size_t lds = (size_t)sort_read_lds_words(a) * 4;
         SortArgs b = a;
         b.lds_words = (uint32_t)(lds / 4);
@@ -4909,14 +4914,15 @@ int launch_sort_read(int stage, const SortArgs& a, hipStream_t st) {
         } else if (gl) SR_LAUNCH(true, 1024);
         else SR_LAUNCH(false, 1024);
 #undef SR_LAUNCH
+    } else if (stage != SortStage::Listed) {
+        return (int)hipErrorInvalidValue;
     } else if (a.cells) {       // the singleton filter is on: every listed read takes the bucket path
         SortArgs b = a;
         b.lds_words = (uint32_t)(SORT_LDS / 4);
         // persistent workgroups on a work counter: one per CU (the LDS allows no
         // more); most batches list no read, and every extra workgroup would wait
         // for a CU the other streams' kernels hold
-        int dev = 0, ncu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        const int ncu = cu_count(256);
         const unsigned grid = std::min<uint32_t>(a.n, (uint32_t)std::max(ncu, 1));
         if (2u * b.n_seq + 2u > (uint32_t)GOFF_LDS) hipLaunchKernelGGL(k_sort_big<true>, dim3(grid), dim3(1024), (size_t)SORT_LDS, st, b);
         else hipLaunchKernelGGL(k_sort_big<false>, dim3(grid), dim3(1024), (size_t)SORT_LDS, st, b);
@@ -4941,13 +4947,17 @@ static size_t giant_lds(int lut_n, uint32_t lcap) {
     return lut_lds(lut_n) + (size_t)cap * GIANT_B;
 }
 static size_t seg_lds(int lut_n) { return lut_lds(lut_n) + (size_t)DP_NW * (KRING * 8 + 3 * TQ * 5 + MEDB * 8); }
-int chain_max_blocks(int lut_n, int which) {
-    int dev = 0, ncu = 0, per = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    hipError_t e = which == 0   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_chain_seg, DP_NW * 64, seg_lds(lut_n))
-                   : which == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_chain_long<false, 4>, DP_NW * 64, chain_lds(lut_n))
-                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_chain_med, 256, lut_lds(lut_n));
+int chain_max_blocks(int lut_n, ChainStage stage) {
+    const int ncu = cu_count(0);
+    if (ncu == 0) return 0;
+    int per = 0;
+    hipError_t e;
+    switch (stage) {
+    case ChainStage::Seg: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_chain_seg, DP_NW * 64, seg_lds(lut_n)); break;
+    case ChainStage::Long: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_chain_long<false, 4>, DP_NW * 64, chain_lds(lut_n)); break;
+    case ChainStage::Med: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_chain_med, 256, lut_lds(lut_n)); break;
+    default: return 0;
+    }
     if (e != hipSuccess) return 0;
     return ncu * (per > 0 ? per : 1);
 }
@@ -4957,34 +4967,33 @@ int launch_read_order(uint32_t n, const uint32_t* a_cnt, uint32_t* order, hipStr
     LAUNCH_CHECK();
     return 0;
 }
-int launch_chain_stage(int stage, const ChainArgs& a, int blocks, hipStream_t st) {
+int launch_chain_stage(ChainStage stage, const ChainArgs& a, int blocks, hipStream_t st) {
     if (a.n == 0) return 0;
     switch (stage) {
-    case 0: hipLaunchKernelGGL(k_chain_seg, dim3(blocks), dim3(DP_NW * 64), seg_lds(a.P.lut_n), st, a); break;
-    case 1: hipLaunchKernelGGL(k_chain_med, dim3(blocks), dim3(256), lut_lds(a.P.lut_n), st, a); break;
-    case 2: hipLaunchKernelGGL(k_lseg_order, dim3(1), dim3(1024), 0, st, a); break;
-    case 3:
+    case ChainStage::Seg: hipLaunchKernelGGL(k_chain_seg, dim3(blocks), dim3(DP_NW * 64), seg_lds(a.P.lut_n), st, a); break;
+    case ChainStage::Med: hipLaunchKernelGGL(k_chain_med, dim3(blocks), dim3(256), lut_lds(a.P.lut_n), st, a); break;
+    case ChainStage::LsegOrder: hipLaunchKernelGGL(k_lseg_order, dim3(1), dim3(1024), 0, st, a); break;
+    case ChainStage::Long:
         if (a.lseg_prof) {
             if (a.spec_batch == 8) hipLaunchKernelGGL((k_chain_long<true, 8>), dim3(blocks), dim3(DP_NW * 64), chain_lds(a.P.lut_n), st, a);
             else hipLaunchKernelGGL((k_chain_long<true, 4>), dim3(blocks), dim3(DP_NW * 64), chain_lds(a.P.lut_n), st, a);
         } else if (a.spec_batch == 8) hipLaunchKernelGGL((k_chain_long<false, 8>), dim3(blocks), dim3(DP_NW * 64), chain_lds(a.P.lut_n), st, a);
         else hipLaunchKernelGGL((k_chain_long<false, 4>), dim3(blocks), dim3(DP_NW * 64), chain_lds(a.P.lut_n), st, a);
         break;
-    case 5: hipLaunchKernelGGL(k_chain_lb, dim3(blocks), dim3(256), lut_lds(a.P.lut_n), st, a); break;
-    case 6: hipLaunchKernelGGL(k_seg_items, dim3(1), dim3(1024), 0, st, a); break;
-    case 10: hipLaunchKernelGGL(k_seg_cands, dim3(blocks), dim3(SC_NW * 64), 0, st, a); break;
-    case 7: {
+    case ChainStage::Lb: hipLaunchKernelGGL(k_chain_lb, dim3(blocks), dim3(256), lut_lds(a.P.lut_n), st, a); break;
+    case ChainStage::Items: hipLaunchKernelGGL(k_seg_items, dim3(1), dim3(1024), 0, st, a); break;
+    case ChainStage::Cands: hipLaunchKernelGGL(k_seg_cands, dim3(blocks), dim3(SC_NW * 64), 0, st, a); break;
+    case ChainStage::Giant: {
         const size_t lds = giant_lds(a.P.lut_n, a.giant_lcap);
         if (blocks <= 0) {   // as many workgroups as fit on the CUs at once (they take segments from a counter)
-            int dev = 0, ncu = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-            blocks = std::max(1, ncu) * (int)std::max<size_t>(1, std::min<size_t>(2, (size_t)(158 * 1024) / std::max<size_t>(lds, 1)));
+            blocks = std::max(1, cu_count(256)) * (int)std::max<size_t>(1, std::min<size_t>(2, (size_t)(158 * 1024) / std::max<size_t>(lds, 1)));
         }
         hipLaunchKernelGGL(k_chain_giant<false>, dim3(blocks), dim3(1024), lds, st, a);
         break;
     }
-    case 8: hipLaunchKernelGGL(k_chain_giant<true>, dim3(blocks), dim3(1024), lut_lds(a.P.lut_n), st, a); break;
-    default: hipLaunchKernelGGL(k_chain_fin, dim3((a.n + 3) / 4), dim3(256), 0, st, a); break;
+    case ChainStage::GiantHbm: hipLaunchKernelGGL(k_chain_giant<true>, dim3(blocks), dim3(1024), lut_lds(a.P.lut_n), st, a); break;
+    case ChainStage::Fin: hipLaunchKernelGGL(k_chain_fin, dim3((a.n + 3) / 4), dim3(256), 0, st, a); break;
+    default: return (int)hipErrorInvalidValue;
     }
     LAUNCH_CHECK();
     return 0;
@@ -4996,16 +5005,15 @@ int launch_dv(const DvArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_dv, dim3(a.n), dim3(64), 0, st, b);
     LAUNCH_CHECK();
     if (b.long_m) {   // reads over DV_LDS minimizers (the host sets long_m only when some may be)
-        int dev = 0, ncu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+        const int ncu = cu_count(256);
         hipLaunchKernelGGL(k_dv_long, dim3(std::min<uint32_t>(a.n, (uint32_t)std::max(ncu, 1))), dim3(1024), (size_t)b.long_m * 4, st, b);
         LAUNCH_CHECK();
     }
     return 0;
 }
 int launch_excl_scan(const uint32_t* in, uint32_t n, uint64_t* out, int mode, int q_occ_max, int k, uint64_t cap, uint32_t* status,
-                     uint32_t bit, int slot, hipStream_t st, uint32_t* order) {
-    hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, st, in, n, out, mode, q_occ_max, k, cap, status, bit, slot, order);
+                     uint32_t bit, StatWord slot, hipStream_t st, uint32_t* order) {
+    hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, st, in, n, out, mode, q_occ_max, k, cap, status, bit, (int)slot, order);
     LAUNCH_CHECK();
     return 0;
 }
@@ -5042,8 +5050,7 @@ int launch_mz_base(uint32_t n, const uint64_t* rd_off, uint64_t* base, uint64_t*
 }
 int launch_mid_hist(const IxEntry* tab, uint64_t cap, uint32_t nbins, unsigned long long* hist, uint32_t* ovf, uint32_t ovf_cap,
                     uint32_t* ovf_n, hipStream_t st) {
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 256;
+    const int ncu = cu_count(256);
     const uint64_t want = (cap + 255) / 256;
     const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)ncu * 8));
     hipLaunchKernelGGL(k_mid_hist, dim3(blocks), dim3(256), nbins * 4, st, tab, cap, nbins, hist, ovf, ovf_cap, ovf_n);
