@@ -953,7 +953,8 @@ __global__ __launch_bounds__(SEED_PARTS * 64) void k_seed_count(SeedArgs a) {
 }
 
 // push_anchor (src/seeds.rs:62-79) packed into the sortable 64-bit key.
-DEVI uint64_t pack_anchor(uint64_t rr, uint32_t my, int32_t qlen, int span, const KeyLayout& kl) {
+// (g, p: the key's group and position, for a caller that needs them unpacked)
+DEVI uint64_t pack_anchor(uint64_t rr, uint32_t my, int32_t qlen, int span, const KeyLayout& kl, uint32_t& g32, uint32_t& p32) {
     const uint32_t rid = (uint32_t)(rr >> 32);
     const uint32_t rpos32 = (uint32_t)(rr >> 1);       // ((r >> 1) & 0xffffffff)
     const uint32_t rstrand = (uint32_t)(rr & 1);
@@ -963,7 +964,12 @@ DEVI uint64_t pack_anchor(uint64_t rr, uint32_t my, int32_t qlen, int span, cons
     uint64_t g; uint32_t p;
     if (rpos32 & 0x80000000u) { g = 2ull * kl.n_seq; p = rpos32 & 0x7fffffffu; }   // Q19 pseudo-group
     else { g = fwd ? (uint64_t)rid : (uint64_t)kl.n_seq + rid; p = rpos32; }
+    g32 = (uint32_t)g; p32 = p;
     return (g << (kl.rb + kl.qb)) | ((uint64_t)p << kl.qb) | (uint64_t)q;
+}
+DEVI uint64_t pack_anchor(uint64_t rr, uint32_t my, int32_t qlen, int span, const KeyLayout& kl) {
+    uint32_t g, p;
+    return pack_anchor(rr, my, qlen, span, kl, g, p);
 }
 
 __global__ __launch_bounds__(256) void k_seed_write(SeedArgs a) {
@@ -1198,6 +1204,35 @@ constexpr int SORT_LDS_HALF = 76 * 1024; // ... two 512-thread workgroups per CU
 #ifndef SORT_FUSE_U
 #define SORT_FUSE_U 16                    // ... in the fused seeding pass (index gathers: more in flight)
 #endif
+
+// Row-bounded rounds of the block-wide passes.  A row is NT consecutive keys,
+// one per thread; [0, n) has n / NT whole rows and, if n % NT, a partly filled
+// last one.  round(i0, R, full) (R an std::integral_constant, full an
+// std::bool_constant) handles rows i0 / NT .. i0 / NT + R - 1, staged: all
+// loads of its R rows, then all uses.  The whole rows go in rounds of U rows,
+// then of U/2, U/4 .. 1 rows, with full = true: every lane has a key, so a
+// round tests no index (ROW_IN folds to true).  The partly filled row is a
+// round of its own with full = false.  No row past n is executed (a read of
+// 20 rows at U = 16 ran 32).  The choice depends on n alone: every branch
+// here is block-uniform (a scalar branch), and round may hold barriers,
+// ballots and shuffles.
+#define ROW_IN(full, i, n) (decltype(full)::value || (i) < (n))
+template <int R, int NT, typename F>
+DEVI void row_tail(uint32_t& i0, uint32_t& rows, F& round) {
+    if constexpr (R >= 1) {
+        while (rows >= (uint32_t)R) {   // (at most once below U when U is a power of two)
+            round(i0, std::integral_constant<int, R>{}, std::true_type{});
+            i0 += (uint32_t)R * NT; rows -= (uint32_t)R;
+        }
+        row_tail<R / 2, NT>(i0, rows, round);
+    }
+}
+template <int U, int NT, typename F>
+DEVI void row_rounds(uint32_t n, F round) {
+    uint32_t rows = n / NT, i0 = 0;
+    row_tail<U, NT>(i0, rows, round);
+    if (n % NT) round(i0, std::integral_constant<int, 1>{}, std::false_type{});
+}
 
 // 8 independent loads per thread, then fn(i, x) for each (i < n): hides HBM
 // latency in the block-wide passes of k_sort_read
@@ -1628,14 +1663,14 @@ __global__ __launch_bounds__(NT) void k_sort_read(SortArgs a) {
             __syncthreads();
             SORT_PH(3);   // MM2G_KNOB_SORT_PROF "fuse_stage": the minimizer staging (the rest of P1 counts as p1)
             const int32_t qlen = (int32_t)(a.rd_off[r + 1] - a.rd_off[r]);
-            constexpr int FU = SORT_FUSE_U;
-            for (uint32_t i0 = 0; i0 < A0; i0 += NT * FU) {
+            row_rounds<SORT_FUSE_U, NT>(A0, [&](uint32_t i0, auto rows, auto full) {
+                constexpr int FU = decltype(rows)::value;
                 uint32_t lo[FU], hi[FU];
 #pragma unroll
                 for (int u = 0; u < FU; ++u) {
-                    const uint32_t t = i0 + (uint32_t)u * NT + tid, b = t < A0 ? t >> 4 : 0u;
+                    const uint32_t t = i0 + (uint32_t)u * NT + tid, b = ROW_IN(full, t, A0) ? t >> 4 : 0u;
                     lo[u] = O16[b];
-                    hi[u] = t >= A0 ? lo[u] : (b + 1 < nb16 ? (uint32_t)O16[b + 1] : fm - 1);
+                    hi[u] = !ROW_IN(full, t, A0) ? lo[u] : (b + 1 < nb16 ? (uint32_t)O16[b + 1] : fm - 1);
                 }
                 // first minimizer from lo with inclusive offset > t (all lanes' searches step together)
                 while (true) {
@@ -1655,7 +1690,7 @@ __global__ __launch_bounds__(NT) void k_sort_read(SortArgs a) {
                 for (int u = 0; u < FU; ++u) {
                     const uint32_t t = i0 + (uint32_t)u * NT + tid;
                     x[u] = 0;
-                    if (t < A0) {
+                    if (ROW_IN(full, t, A0)) {
                         const uint32_t ow = lo[u];
                         const uint32_t h = Mh[ow], exo = ow ? Mi[ow - 1] : 0u;
                         x[u] = (h & IX_INLINE) ? ((uint64_t)(h & ~IX_INLINE) << 32) | Mp[ow]   // Single: no gather
@@ -1666,43 +1701,45 @@ __global__ __launch_bounds__(NT) void k_sort_read(SortArgs a) {
 #pragma unroll
                 for (int u = 0; u < FU; ++u) {
                     const uint32_t t = i0 + (uint32_t)u * NT + tid;
-                    x[u] = pack_anchor(x[u], My[lo[u]], qlen, a.span, a.kl);
-                    if (t < A0) K[t] = x[u];
-                    c[u] = cell_of(x[u]);
+                    uint32_t g, p;
+                    x[u] = pack_anchor(x[u], My[lo[u]], qlen, a.span, a.kl, g, p);
+                    if (ROW_IN(full, t, A0)) K[t] = x[u];
+                    c[u] = (GL ? a.goff[g] : s_goff[g]) + 1u + (p >> CELL_SHIFT);   // cell_of(x[u]) without unpacking
                 }
 #pragma unroll
                 for (int u = 0; u < FU; ++u) {
                     const uint32_t t = i0 + (uint32_t)u * NT + tid;
-                    lo[u] = t < A0 ? atomicOr(&B1[c[u] >> 5], 1u << (c[u] & 31)) : 0u;   // (lo: the old words)
+                    lo[u] = ROW_IN(full, t, A0) ? atomicOr(&B1[c[u] >> 5], 1u << (c[u] & 31)) : 0u;   // (lo: the old words)
                 }
 #pragma unroll
                 for (int u = 0; u < FU; ++u) {
                     const uint32_t t = i0 + (uint32_t)u * NT + tid, bit = 1u << (c[u] & 31);
-                    if (t < A0 && (lo[u] & bit)) atomicOr(&B2[c[u] >> 5], bit);
+                    if (ROW_IN(full, t, A0) && (lo[u] & bit)) atomicOr(&B2[c[u] >> 5], bit);
                 }
-            }
+            });
         } else {
         __syncthreads();
         // staged per group of SORT_U1 keys: all cells, then all first atomics
         // (LDS round trips overlap instead of one chain per key)
-        for (uint32_t i0 = 0; i0 < A0; i0 += NT * SORT_U1) {
-            uint64_t x[SORT_U1];
-            uint32_t c[SORT_U1], old[SORT_U1];
+        row_rounds<SORT_U1, NT>(A0, [&](uint32_t i0, auto rows, auto full) {
+            constexpr int R = decltype(rows)::value;
+            uint64_t x[R];
+            uint32_t c[R], old[R];
 #pragma unroll
-            for (int u = 0; u < SORT_U1; ++u) { const uint32_t i = i0 + (uint32_t)u * NT + tid; x[u] = i < A0 ? K[i] : 0; }
+            for (int u = 0; u < R; ++u) { const uint32_t i = i0 + (uint32_t)u * NT + tid; x[u] = ROW_IN(full, i, A0) ? K[i] : 0; }
 #pragma unroll
-            for (int u = 0; u < SORT_U1; ++u) c[u] = cell_of(x[u]);
+            for (int u = 0; u < R; ++u) c[u] = cell_of(x[u]);
 #pragma unroll
-            for (int u = 0; u < SORT_U1; ++u) {
+            for (int u = 0; u < R; ++u) {
                 const uint32_t i = i0 + (uint32_t)u * NT + tid;
-                old[u] = i < A0 ? atomicOr(&B1[c[u] >> 5], 1u << (c[u] & 31)) : 0u;
+                old[u] = ROW_IN(full, i, A0) ? atomicOr(&B1[c[u] >> 5], 1u << (c[u] & 31)) : 0u;
             }
 #pragma unroll
-            for (int u = 0; u < SORT_U1; ++u) {
+            for (int u = 0; u < R; ++u) {
                 const uint32_t i = i0 + (uint32_t)u * NT + tid, bit = 1u << (c[u] & 31);
-                if (i < A0 && (old[u] & bit)) atomicOr(&B2[c[u] >> 5], bit);   // seen before: seen twice
+                if (ROW_IN(full, i, A0) && (old[u] & bit)) atomicOr(&B2[c[u] >> 5], bit);   // seen before: seen twice
             }
-        }
+        });
         }
         __syncthreads();
         // ---- KC (in place of B2) and the word prefix of its popcounts (in place of B1)
@@ -1736,7 +1773,8 @@ __global__ __launch_bounds__(NT) void k_sort_read(SortArgs a) {
             uint64_t* S = dyn64;
             for (uint32_t i = tid; i < cw; i += NT) C[i] = 0;
             __syncthreads();
-            auto c16 = [&](uint32_t rk) -> uint32_t { return (C[rk >> 1] >> ((rk & 1) << 4)) & 0xffffu; };
+            // count / offset of kept cell rk: one u16 load (the atomics add 1 << 16 (rk & 1) to word rk >> 1)
+            auto c16 = [&](uint32_t rk) -> uint32_t { return ((const uint16_t*)C)[rk]; };
             // ---- P2: counts per kept cell; the largest dropped key.  Each key's
             // kept-cell rank (0xffff = dropped) goes to the u16 tag array T16 in
             // the DP's f buffer, so the window passes need no cell lookups (and
@@ -1744,19 +1782,20 @@ __global__ __launch_bounds__(NT) void k_sort_read(SortArgs a) {
             uint64_t smx = 0;
             uint16_t* T16 = (uint16_t*)(a.meta + base);
             // staged like P1: all cells, all bitmap reads, then counts and tags
-            for (uint32_t i0 = 0; i0 < A0; i0 += NT * SORT_U2) {
-                uint64_t x[SORT_U2];
-                uint32_t c[SORT_U2], kw[SORT_U2], pw[SORT_U2];
+            row_rounds<SORT_U2, NT>(A0, [&](uint32_t i0, auto rows, auto full) {
+                constexpr int R = decltype(rows)::value;
+                uint64_t x[R];
+                uint32_t c[R], kw[R], pw[R];
 #pragma unroll
-                for (int u = 0; u < SORT_U2; ++u) { const uint32_t i = i0 + (uint32_t)u * NT + tid; x[u] = i < A0 ? K[i] : 0; }
+                for (int u = 0; u < R; ++u) { const uint32_t i = i0 + (uint32_t)u * NT + tid; x[u] = ROW_IN(full, i, A0) ? K[i] : 0; }
 #pragma unroll
-                for (int u = 0; u < SORT_U2; ++u) c[u] = cell_of(x[u]);
+                for (int u = 0; u < R; ++u) c[u] = cell_of(x[u]);
 #pragma unroll
-                for (int u = 0; u < SORT_U2; ++u) { kw[u] = B2[c[u] >> 5]; pw[u] = B1[c[u] >> 5]; }
+                for (int u = 0; u < R; ++u) { kw[u] = B2[c[u] >> 5]; pw[u] = B1[c[u] >> 5]; }
 #pragma unroll
-                for (int u = 0; u < SORT_U2; ++u) {
+                for (int u = 0; u < R; ++u) {
                     const uint32_t i = i0 + (uint32_t)u * NT + tid;
-                    if (i < A0) {
+                    if (ROW_IN(full, i, A0)) {
                         const uint32_t b = c[u] & 31;
                         const bool kept = (kw[u] >> b) & 1u;
                         const uint32_t rk = pw[u] + (uint32_t)__popc(kw[u] & ((1u << b) - 1u));
@@ -1765,7 +1804,7 @@ __global__ __launch_bounds__(NT) void k_sort_read(SortArgs a) {
                         T16[i] = kept ? (uint16_t)rk : (uint16_t)0xffffu;
                     }
                 }
-            }
+            });
             smx = block_max64<NW>(smx, red);               // (its barriers also end the count atomics)
             // exclusive scan of the u16 counts, in place (offsets < A0 <= 65535)
             const uint32_t per2 = (cw + NT - 1) / NT;
